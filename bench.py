@@ -20,7 +20,13 @@ GPUs itself (option "devices", RCCL all-gather + all-reduce(MIN) inside the libr
 Shadow process would.  Under torchrun only rank 0 works in this mode; the other ranks wait.
 --mode torchrun: one process per GPU builds its row shard and torch.distributed (RCCL) exchanges.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]   (N GPUs from one process), or
+A plain run does what the headline figure needs: it generates and loads the topology, attaches
+the hosts, builds the first table, warms up, times --steps builds and prints the result line.
+--full adds everything measured or checked beside it (GraphML round-trip comparison, packet-route
+window, getters block, CPU baselines, C2/C3 table lines, C4-dir line); those fields are null in a
+plain run's line.  --dump-outputs DIR writes the last timed step's table as DIR/<name>.npy.
+
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR], or
         python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 """
 import argparse
@@ -377,6 +383,42 @@ def hbm_roofline(kernel, kernel_ms, traffic_pm, model_bytes_per_unit, units, mod
     return out
 
 
+DUMP_PAIRS = 2_000_000         # pairs of a large table that --dump-outputs keeps (28 B each)
+
+
+def dump_outputs(out_dir, top, table, gmin):
+    """--dump-outputs: what the last timed step left for its caller -- the attached-vertex table
+    (latency ms, reliability, hops per pair) and the runahead minimum latency -- as
+    <out_dir>/<name>.npy.  A table of more than DUMP_PAIRS pairs is sampled at DUMP_PAIRS flat
+    pair indices drawn from SEED (pair_index.npy: row * A + column), the same in every run.
+    `table` is the torchrun mode's ShardedTable (device tensors), None in library mode (the
+    library's installed table is copied to the host)."""
+    os.makedirs(out_dir, exist_ok=True)
+    attached = top.attached_vertices()
+    A = len(attached)
+    if A * A > DUMP_PAIRS:
+        idx = np.sort(np.random.default_rng(SEED).integers(0, A * A, DUMP_PAIRS))
+    else:
+        idx = np.arange(A * A, dtype=np.int64)
+    if table is None:
+        _, lat, rel, hops = top.table()
+        lat, rel, hops = lat.ravel()[idx], rel.ravel()[idx], hops.ravel()[idx]
+    else:
+        lr, h = table.table()
+        i = torch.from_numpy(idx).to(lr.device)
+        rec = lr.reshape(-1, 2)[i].cpu().numpy()
+        lat, rel = rec[:, 0], rec[:, 1]
+        hops = h.reshape(-1)[i].cpu().numpy().view(np.uint16)
+    arrays = dict(attached_vertices=attached.astype(np.float64),
+                  pair_index=idx.astype(np.float64),
+                  latency_ms=np.ascontiguousarray(lat, np.float64),
+                  reliability=np.ascontiguousarray(rel, np.float64),
+                  hops=hops.astype(np.float32),
+                  min_latency_ms=np.array([gmin], np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -408,7 +450,16 @@ def main():
     ap.add_argument("--batch", type=int, default=8, help="sources per SSSP workgroup (2/4/8/16)")
     ap.add_argument("--opt", action="append", default=[], help="key=value library option")
     ap.add_argument("--pmc-tag", default=PROFILE_TAG)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the GraphML round-trip "
+                         "check, the packet-route window, the getters block, the CPU baselines, "
+                         "the C2/C3 table lines and the C4-dir line (each has its own switch above)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's table (a seeded sample of "
+                         "its pairs when it is large) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -461,11 +512,12 @@ def main():
             top = sa.Topology.new(path)
             graphml["load_s"] = round(time.time() - t1, 2)
             assert top is not None, "topology_new failed on the written GraphML"
-            a_, b_ = gen.export_graph(), top.export_graph()
-            assert a_[0] == b_[0] and all(np.array_equal(np.asarray(x).view(np.uint8),
-                                                         np.asarray(y).view(np.uint8))
-                                          for x, y in zip(a_[1:], b_[1:])), "GraphML round trip"
-            graphml["round_trip_bit_exact"] = True
+            if args.full:
+                a_, b_ = gen.export_graph(), top.export_graph()
+                assert a_[0] == b_[0] and all(np.array_equal(np.asarray(x).view(np.uint8),
+                                                             np.asarray(y).view(np.uint8))
+                                              for x, y in zip(a_[1:], b_[1:])), "GraphML round trip"
+                graphml["round_trip_bit_exact"] = True
         finally:
             if torchrun:
                 dist.barrier()
@@ -560,9 +612,10 @@ def main():
     # the packet window (same seed chain: every host re-attaches to the same vertex, the table
     # stays valid), then the timed steps
     tw0 = time.time()
-    pk = top.synth_packets(SEED, args.hosts, args.packets, 10**9, window0)
+    n_packets = args.packets if args.full else 0   # a plain run re-attaches only
+    pk = top.synth_packets(SEED, args.hosts, n_packets, 10**9, window0)
     log(rank, "workload ready (window of %d packets in %.1fs): V=%d E=%d A=%d, %d GPU(s), mode %s"
-        % (args.packets, time.time() - tw0, V, E, A, ngpu, args.mode))
+        % (n_packets, time.time() - tw0, V, E, A, ngpu, args.mode))
     kernel_ms.clear()
     replay_ms.clear()
     for _ in range(args.warmup):
@@ -580,8 +633,12 @@ def main():
     jump = int(gmin) * 1_000_000 if gmin >= 1.0 else window0   # shd-master.c:113-124
     gteps = A * E / t_step / 1e9
 
+    # ---- the last step's table, for comparing two builds output for output ----
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, top, None if library else table, gmin)
+
     # ---- packet routes: the window split over the GPUs, inputs resident in HBM ----
-    nslice = ngpu if library else 1
+    nslice = (ngpu if library else 1) if args.full else 0   # --full only
     sl = []
     for s in range(nslice):
         p0, p1 = sharding.packet_range(args.packets, s if library else rank,
@@ -607,19 +664,21 @@ def main():
                                        x["t"], x["s"], x["dl"],
                                        stream=torch.cuda.current_stream().cuda_stream)
     route_ms = []
-    for i in range(2 + args.route_steps):
+    for i in range(2 + args.route_steps if args.full else 0):
         if i == 2:
             barrier()
             tr0 = time.perf_counter()
         route_once()
         if i >= 2:
             route_ms.append(top.stats()["route_kernel_ms"])  # slot 0's launch
-    barrier()
-    t_window = max_over_ranks(time.perf_counter() - tr0) / args.route_steps
-    routes_per_s = args.packets / t_window
+    t_window = routes_per_s = None
+    if args.full:
+        barrier()
+        t_window = max_over_ranks(time.perf_counter() - tr0) / args.route_steps
+        routes_per_s = args.packets / t_window
 
     getters = None
-    if library and rank == 0 and args.getter_queries > 0:
+    if args.full and library and rank == 0 and args.getter_queries > 0:
         log(rank, "getters block: %d queries..." % args.getter_queries)
         getters = getters_block(top, pk, args.getter_queries, cpu_share(),
                                 cpu=ngpu == 1 and not args.no_cpu_baseline)
@@ -740,7 +799,7 @@ def main():
                 route_roof["traffic_over_model"] = round(rpm["hbm_bytes_per_launch"] /
                                                          (53 * sl[0]["n"]), 3)
         cpu = None
-        if ngpu == 1 and not args.no_cpu_baseline:
+        if args.full and ngpu == 1 and not args.no_cpu_baseline:
             nt = cpu_share()
             log(rank, "cpu baseline: %d sources on 1 thread, %d on %d threads..." % (
                 args.cpu_sample, args.cpu_sample_mt, nt))
@@ -759,13 +818,13 @@ def main():
             cpu["host_nproc"] = os.cpu_count()
             cpu["job_cpu_share"] = nt
         complete = None
-        if library and not args.no_complete:
+        if args.full and library and not args.no_complete:
             # configs 2 / 3 on the job's GPUs (option devices = N; "--opt devices=N" rehearses the
             # N-engine path on one GPU, the engines then sharing it)
             ndev = int(float(dict(kv.split("=") for kv in args.opt).get("devices", ngpu)))
             complete = complete_table_lines(nthreads=cpu_share(), devices=ndev, cpu=ngpu == 1)
         directed = None
-        if library and ngpu == 1 and not args.no_directed and not args.integer:
+        if args.full and library and ngpu == 1 and not args.no_directed and not args.integer:
             # after the main topology's buffers are gone (its workspace holds ~110 GB)
             top.free()
             torch.cuda.empty_cache()
@@ -798,8 +857,9 @@ def main():
                                      "all-gather + all-reduce(min)" % world),
             },
             "cold_build": cold,
-            "packet_routes_per_s": round(routes_per_s, 1),
-            "ms_per_window": round(t_window * 1e3, 4),
+            "full": args.full,
+            "packet_routes_per_s": round(routes_per_s, 1) if args.full else None,
+            "ms_per_window": round(t_window * 1e3, 4) if args.full else None,
             "roofline": roofline,
             "route_roofline": route_roof,
             "getters": getters,

@@ -9,7 +9,6 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-REF_RESOURCE = "/root/reference/resource"
 
 
 def pytest_configure(config):
@@ -18,11 +17,9 @@ def pytest_configure(config):
 
 
 def bundled_topology(name):
-    """Bundled topology XML bytes.  The GPU box has no /root/reference, so the three bundled
-    files are vendored as data fixtures (xz, byte-identical) under tests/golden/resource/."""
+    """Bundled topology XML bytes: the reference's three bundled files, kept as data fixtures
+    (xz, byte-identical) under tests/golden/resource/."""
     p = os.path.join(GOLDEN, "resource", name + ".graphml.xml.xz")
-    if not os.path.exists(p):
-        p = os.path.join(REF_RESOURCE, name + ".graphml.xml.xz")
     with lzma.open(p) as f:
         return f.read()
 

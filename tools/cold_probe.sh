@@ -6,7 +6,7 @@ set -u
 OUT=$1
 ROOT=$(pwd)
 mkdir -p "$OUT"
-ARGS=(--no-cpu-baseline --no-complete --no-directed --route-steps 1 --getter-queries 0)
+ARGS=(--full --no-cpu-baseline --no-complete --no-directed --route-steps 1 --getter-queries 0)
 timeout -k 10 400 python3 -u bench.py --steps 3 --warmup 1 "${ARGS[@]}" > "$OUT/bench.json" 2> "$OUT/bench.log" || exit $?
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d "$ROOT/$OUT/prof" -o cold -- \

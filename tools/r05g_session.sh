@@ -8,4 +8,4 @@ for cfg in "1250 1" "1250 0" "10000 1" "10000 0"; do
   python3 tools/batch_trace.py $O/trace_$1_$2.bin > $O/trace_$1_$2.txt 2>&1
   rm -f $O/trace_$1_$2.bin
 done
-timeout -k 10 500 python -u bench.py --opt devices=8 --no-cpu-baseline --steps 2 --route-steps 5 > $O/bench_dev8.json 2> $O/bench_dev8.log
+timeout -k 10 500 python -u bench.py --full --opt devices=8 --no-cpu-baseline --steps 2 --route-steps 5 > $O/bench_dev8.json 2> $O/bench_dev8.log
