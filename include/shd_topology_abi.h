@@ -132,7 +132,9 @@ Topology* shdtopo_new_from_buffer(const char* graphml, size_t len);
  * workgroup and the board-less kernel runs; -1: the board for a launch whose batches fit one
  * round of the slots), "balance" (1, the default: from the second batched build of a graph on,
  * batches are sized (one round of the slots) or dequeued longest first (several rounds) by the
- * sources' costs measured from the earlier builds' batch times; 0: the grouping order only).
+ * sources' costs measured from the earlier builds' batch times; 0: the grouping order only),
+ * "trace_chunk" (sources per replay launch of shdtopo_trace_routes; 0, the default: the replay's
+ * wavefront slots; a small value forces several chunks -- a test hook).
  * Returns 0 or -1 for an unknown key / bad value. */
 int shdtopo_set_option(Topology* top, const char* key, double value);
 
@@ -414,6 +416,66 @@ int shdtopo_test_segsort(const uint32_t* rowptr, int64_t nseg, const float* keys
  * stopping when every attached vertex is popped.  dist f64[V] (-1 = unreached) and parent int32[V]
  * (-1 = none) receive the replay's result in original vertex ids.  Returns 0 or an error. */
 int shdtopo_replay_source(Topology* top, int32_t src, int full, double* dist, int32_t* parent);
+
+/* ---- route tracing: the vertex / edge path behind a table entry ----
+ * The reference logs it at debug level for every pair it computes (shd-topology.c:594,644,
+ * 654-656).  A trace answers "which route does host A take to host B, and which link contributes
+ * the 40 ms" without touching the table. */
+typedef struct {
+    int64_t offset;      /* first entry of this route in vertices[] / edges[]; -1 if not written */
+    int32_t hops;        /* edges on the route (self pair: 1, the self loop); -1 if not traced    */
+    int32_t status;      /* 0 ok, 1 src or dst not attached, 2 unroutable / broken chain,
+                            3 route longer than the space left (cap)                             */
+    double  latency;     /* re-accumulated along the route, the helper's order and zero rule     */
+    double  reliability; /* ((1*(1-p_src))*(1-p_dst))*prod(1-p_e) from the source end            */
+} ShdRoute;
+
+/* Trace the routes of n (source, destination) host pairs (IPs in network order; duplicate and
+ * unsorted requests are fine).  Route i takes hops + 1 entries at routes[i].offset:
+ * vertices[offset .. offset + hops] are original vertex indices, source first, destination last;
+ * edges[offset + k] is the edge between vertices[offset + k] and vertices[offset + k + 1] (edge id
+ * = document order = igraph's id; of a parallel group the lowest id, as igraph_get_eid), and
+ * edges[offset + hops] = -1.  Two hosts on one vertex (or src == dst) take the self loop:
+ * vertices [v, v], hops 1; no self loop: status 2.  Offsets are the running sum of hops + 1 over
+ * the requests in request order, and the return value is the number of entries all routes need,
+ * so a call with cap = 0 (vertices / edges may then be NULL) sizes the buffers.  With a cap that
+ * is too small the routes that fit entirely are written; the rest get status 3 and offset -1
+ * (hops, latency and reliability still filled), and nothing at or beyond cap is touched.
+ * Requests with status 1 or 2 have hops -1, offset -1, latency = reliability = -1.0.
+ *
+ * The route is always the forward route of the SOURCE's row for the current attached set:
+ * latency, reliability and hops equal shdtopo_table_to_host at [col(src)][col(dst)] bit for bit.
+ * In lazy mode on an undirected topology topology_getLatency(a, b) may be answered from row b
+ * (first-rooted-wins, shd-topology.c:896-915) and then equals trace(b, a), not trace(a, b).
+ *
+ * SSSP topologies: the distinct sources run through the exact heap replay (seconds per source
+ * at a million vertices), in chunks of at most its wavefront slots (option
+ * "trace_chunk"); the first trace uploads the edge ids (4 B per adjacency entry).  Complete
+ * topologies (_topology_lookupPath, :835-873: one hop over the direct edge) are answered on the
+ * host from the parsed graph: no device, no table.  A multi-device topology traces on its first
+ * device.  A trace materialises no lazy row, pushes no minimum, neither invalidates nor rebuilds
+ * the table and leaves ShdStats as it was.  Returns a negative value on an error (-1: bad
+ * arguments). */
+int64_t shdtopo_trace_routes(Topology* top, const uint32_t* srcIP, const uint32_t* dstIP, int64_t n,
+                             ShdRoute* routes, int32_t* vertices, int32_t* edges, int64_t cap);
+/* Host-only: the text of the reference's debug line for route r (status 0, written) --
+ * "shortest path %s-->%s (%i-->%i) is %f ms with %f loss, path: %s" with the vertices' GraphML
+ * ids and, per hop, "--[%f,%f]-->%s" = [edge latency, 1 - edge packetloss].  Writes at most cap
+ * bytes (NUL-terminated when cap > 0) and returns the length needed (without the NUL), or -1. */
+int64_t shdtopo_format_route(Topology* top, const ShdRoute* r, const int32_t* vertices,
+                             const int32_t* edges, char* buf, size_t cap);
+/* the last trace's own counters (ShdStats is not touched by a trace) */
+typedef struct {
+    double total_ms;        /* wall time of the call */
+    double replay_ms;       /* event time of its heap-replay launches */
+    double trace_kernel_ms; /* event time of route_trace_kernel, its scans, placement and scatter */
+    double ids_ms;          /* wall time of the edge-id upload (first trace of a topology, else 0) */
+    int64_t requests;       /* n */
+    int64_t sources;        /* distinct source vertices replayed */
+    int64_t chunks;         /* replay launches */
+    int64_t entries;        /* the call's return value */
+} ShdTraceStats;
+int shdtopo_trace_stats(Topology* top, ShdTraceStats* out);
 
 /* Test hook: the device graph preparation (topo_prep.hip) read back -- perm
  * int32[V] (relabelled -> original vertex), rowptr u32[V+1], the adjacency columns u32[2E']

@@ -64,6 +64,16 @@ class ShdStats(ctypes.Structure):
                 ("exchange_exposed_ms", dbl), ("workspace_bytes", i64)]
 
 
+class ShdRoute(ctypes.Structure):
+    _fields_ = [("offset", i64), ("hops", i32), ("status", i32), ("latency", dbl),
+                ("reliability", dbl)]
+
+
+class ShdTraceStats(ctypes.Structure):
+    _fields_ = [("total_ms", dbl), ("replay_ms", dbl), ("trace_kernel_ms", dbl), ("ids_ms", dbl),
+                ("requests", i64), ("sources", i64), ("chunks", i64), ("entries", i64)]
+
+
 class ShdSynthParams(ctypes.Structure):
     _fields_ = [("seed", u64), ("n_routers", i64), ("n_poi", i64), ("n_edges", i64),
                 ("integer_latency", ctypes.c_int), ("alpha", dbl), ("directed", ctypes.c_int)]
@@ -115,6 +125,9 @@ SIGNATURES = {
     "shdtopo_get_stats": (ctypes.c_int, [P, P]),
     "shdtopo_write_graphml": (ctypes.c_int, [P, cstr]),
     "shdtopo_replay_source": (ctypes.c_int, [P, i32, ctypes.c_int, P, P]),
+    "shdtopo_trace_routes": (i64, [P, P, P, i64, P, P, P, i64]),
+    "shdtopo_format_route": (i64, [P, P, P, P, P, ctypes.c_size_t]),
+    "shdtopo_trace_stats": (ctypes.c_int, [P, P]),
     "shdtopo_test_segsort": (ctypes.c_int, [P, i64, P, i64, ctypes.c_int, P, P]),
     "shdtopo_test_batch_layout": (ctypes.c_int, [P, i64, dbl, ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_int, P, P, P]),

@@ -446,6 +446,14 @@ struct _Topology {
     hipEvent_t evr0 = nullptr, evr1 = nullptr;
     bool replayPending = false;
 
+    // route tracing (shdtopo_trace_routes, topo_trace.hip): ids the replay CSR does not carry,
+    // uploaded by the first trace -- relabelled -> original vertex, the igraph_get_eid edge of
+    // every replay-CSR entry, the lowest-id self loop of every vertex
+    int traceChunk = 0;       // option "trace_chunk": sources per replay launch (0 = the slots)
+    bool traceIdsReady = false;
+    DevBuf<int32_t> d_tperm, d_reid, d_selfEid;
+    ShdTraceStats traceStats{};  // the last trace's own counters
+
     // multi-GPU build inside the library (one Shadow process): device d builds
     // rows [d*R, (d+1)*R) with its own stream / workspace (a peer Topology on that device),
     // RCCL all-gathers the rows into every device's table and all-reduces the minimum
@@ -3371,6 +3379,10 @@ int shdtopo_set_option(Topology* top, const char* key, double value) {
     else if (k == "replay_wpc") top->replayWpc = std::max(1, std::min(64, (int)value));
     else if (k == "replay_landmark") top->replayLandmark = value != 0;
     else if (k == "replay_int_keys") top->replayIntOpt = value != 0;
+    else if (k == "trace_chunk") {
+        if (!(value >= 0 && value <= 1e9)) return -1;
+        top->traceChunk = (int)value;
+    }
     else if (k == "tie_dense") top->tieDenseOpt = value < 0 ? -1 : (value != 0 ? 1 : 0);
     else if (k == "source_order") top->sourceOrder = (int)value;
     else if (k == "batch_order") top->batchOrder = (int)value;
@@ -4019,6 +4031,391 @@ int shdtopo_replay_source(Topology* top, int32_t srcv, int full, double* dist, i
         parent[o] = hp[i] < 0 ? -1 : top->hp->perm[(size_t)hp[i]];
     }
     return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// route tracing (include/shd_topology_abi.h shdtopo_trace_routes; kernels in topo_trace.hip)
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+static_assert(sizeof(ShdRoute) == 32 && sizeof(TraceRoute) == sizeof(ShdRoute) &&
+                  offsetof(ShdRoute, hops) == offsetof(TraceRoute, hops) &&
+                  offsetof(ShdRoute, status) == offsetof(TraceRoute, status) &&
+                  offsetof(ShdRoute, latency) == offsetof(TraceRoute, latency) &&
+                  offsetof(ShdRoute, reliability) == offsetof(TraceRoute, reliability),
+              "TraceRoute is the device image of ShdRoute");
+
+ShdRoute route_blank(int status) {
+    ShdRoute r;
+    r.offset = -1;
+    r.hops = -1;
+    r.status = status;
+    r.latency = -1.0;
+    r.reliability = -1.0;
+    return r;
+}
+
+// The call's offsets on the host (complete topologies): the running sum of hops + 1 over the
+// traced requests in request order; a route that does not fit below cap entirely gets status 3.
+int64_t place_routes_host(ShdRoute* routes, int64_t n, int64_t cap) {
+    int64_t off = 0;
+    for (int64_t i = 0; i < n; i++) {
+        if (routes[i].status != kTraceOk) continue;
+        const int64_t need = (int64_t)routes[i].hops + 1;
+        if (off + need <= cap) {
+            routes[i].offset = off;
+        } else {
+            routes[i].offset = -1;
+            routes[i].status = kTraceCap;
+        }
+        off += need;
+    }
+    return off;
+}
+
+// _topology_lookupPath (shd-topology.c:835-873) with its route: one hop over the igraph_get_eid
+// edge (lowest id) of the pair, the self loop for a self pair.  Host only: the parsed graph.
+int64_t trace_complete(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
+                       int64_t n, ShdRoute* routes, int32_t* vertices, int32_t* edges, int64_t cap) {
+    const HostGraph& g = top->g;
+    auto key = [](int32_t a, int32_t b) { return ((uint64_t)(uint32_t)a << 32) | (uint32_t)b; };
+    std::unordered_map<uint64_t, int32_t> eidOf;
+    for (int64_t i = 0; i < n; i++)
+        if (sv[(size_t)i] >= 0 && dv[(size_t)i] >= 0) eidOf.emplace(key(sv[(size_t)i], dv[(size_t)i]), -1);
+    for (int64_t e = 0; e < g.E; e++) {
+        const int32_t a = g.eu[(size_t)e], b = g.ev[(size_t)e];
+        auto it = eidOf.find(key(a, b));
+        if (it != eidOf.end() && it->second < 0) it->second = (int32_t)e;
+        if (!g.directed) {
+            it = eidOf.find(key(b, a));
+            if (it != eidOf.end() && it->second < 0) it->second = (int32_t)e;
+        }
+    }
+    std::vector<int32_t> eids((size_t)n, -1);
+    for (int64_t i = 0; i < n; i++) {
+        const int32_t s = sv[(size_t)i], d = dv[(size_t)i];
+        if (s < 0 || d < 0) {
+            routes[i] = route_blank(kTraceUnattached);
+            continue;
+        }
+        const int32_t e = eidOf[key(s, d)];
+        if (e < 0) {  // igraph_get_eid fails (shd-topology.c:857)
+            routes[i] = route_blank(kTraceBroken);
+            continue;
+        }
+        eids[(size_t)i] = e;
+        double rel = 1.0;
+        rel *= (1.0 - g.vloss[(size_t)s]);
+        rel *= (1.0 - g.vloss[(size_t)d]);
+        double lat = 0.0;
+        lat += g.elat[(size_t)e];
+        rel *= (1.0 - g.eloss[(size_t)e]);
+        routes[i].offset = -1;
+        routes[i].hops = 1;
+        routes[i].status = kTraceOk;
+        routes[i].latency = lat;
+        routes[i].reliability = rel;
+    }
+    const int64_t total = place_routes_host(routes, n, cap);
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t o = routes[i].offset;
+        if (routes[i].status != kTraceOk || o < 0) continue;
+        vertices[o] = sv[(size_t)i];
+        vertices[o + 1] = dv[(size_t)i];
+        edges[o] = eids[(size_t)i];
+        edges[o + 1] = -1;
+    }
+    return total;
+}
+
+// ids of the replay CSR's vertices and entries (TraceIds), once per topology: at C4 the edge ids
+// are 80 MB, so the first trace uploads them, not the build.  Caller holds buildMu; the replay
+// CSR is uploaded.
+int ensure_trace_ids(Topology* top, double* ms) {
+    if (top->traceIdsReady) return 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    const HostGraph& g = top->g;
+    const size_t V = (size_t)g.V;
+    hipStream_t st = top->stream;
+    HIPCHK(top->d_tperm.ensure(V));
+    HIPCHK(hipMemcpy(top->d_tperm.p, top->hp->perm.data(), 4 * V, hipMemcpyHostToDevice));
+    std::vector<int32_t> se(V, -1);  // lowest-id self loop per relabelled vertex
+    for (int64_t e = 0; e < g.E; e++) {
+        if (g.eu[(size_t)e] != g.ev[(size_t)e]) continue;
+        int32_t& x = se[(size_t)top->hp->inv[(size_t)g.eu[(size_t)e]]];
+        if (x < 0) x = (int32_t)e;
+    }
+    HIPCHK(top->d_selfEid.ensure(V));
+    HIPCHK(hipMemcpy(top->d_selfEid.p, se.data(), 4 * V, hipMemcpyHostToDevice));
+    HIPCHK(top->d_reid.ensure((size_t)std::max<int64_t>(1, top->rnadj)));
+    HIPCHK(launch_trace_edge_ids(g.V, g.E, top->isDirected ? 1 : 0, top->d_eu.p, top->d_ev.p,
+                                 top->d_inv.p, top->d_tperm.p, top->d_rrow.p, top->d_rrec.p,
+                                 top->rnadj, top->d_reid.p, st));
+    HIPCHK(hipStreamSynchronize(st));
+    top->traceIdsReady = true;
+    *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
+}
+
+// a trace leaves the last build's statistics and the replay's launch width as they were
+struct TraceKeep {
+    Topology* top;
+    ShdStats stats;
+    int rslotsUse;
+    explicit TraceKeep(Topology* t) : top(t), stats(t->stats), rslotsUse(t->rslotsUse) {}
+    ~TraceKeep() {
+        top->stats = stats;
+        top->rslotsUse = rslotsUse;
+    }
+};
+struct TraceEvents {
+    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+    ~TraceEvents() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+};
+
+// SSSP topologies: replay the distinct sources in chunks, walk the requests' chains (topo_trace.hip)
+int64_t trace_replay(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
+                     int64_t n, ShdRoute* routes, int32_t* vertices, int32_t* edges, int64_t cap,
+                     ShdTraceStats* ts) {
+    int r = dev_init(top);
+    if (r) return r;
+    r = collect_row_stats(top);  // the last build's counters are read before the replay is reused
+    if (r) return r;
+    TraceKeep keep(top);
+    r = upload_csr(top);
+    if (r) return r;
+    r = upload_replay(top);
+    if (r) return r;
+    r = ensure_trace_ids(top, &ts->ids_ms);
+    if (r) return r;
+    hipStream_t st = top->stream;
+    const std::vector<int32_t>& inv = top->hp->inv;
+
+    // requests sorted by source (stable: request order within a source), CSR over the sources
+    std::vector<uint32_t> order;
+    for (int64_t i = 0; i < n; i++)
+        if (sv[(size_t)i] >= 0 && dv[(size_t)i] >= 0) order.push_back((uint32_t)i);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        return inv[(size_t)sv[a]] < inv[(size_t)sv[b]];
+    });
+    const size_t nv = order.size();
+    std::vector<uint32_t> srcs, srcStart, rsi(nv), rsrc(nv), rdst(nv);
+    for (size_t q = 0; q < nv; q++) {
+        const uint32_t s = (uint32_t)inv[(size_t)sv[order[q]]];
+        if (srcs.empty() || srcs.back() != s) {
+            srcs.push_back(s);
+            srcStart.push_back((uint32_t)q);
+        }
+        rsi[q] = (uint32_t)srcs.size() - 1u;
+        rsrc[q] = s;
+        rdst[q] = (uint32_t)inv[(size_t)dv[order[q]]];
+    }
+    srcStart.push_back((uint32_t)nv);
+    const int nsrc = (int)srcs.size();
+    ts->sources = nsrc;
+
+    // the table build's target set: the chains are the table's chains
+    r = ensure_replay_ws(top, nsrc);
+    if (r) return r;
+    const int64_t A = top->A;
+    std::vector<uint32_t> tgt((size_t)A);
+    for (int64_t i = 0; i < A; i++) tgt[(size_t)i] = (uint32_t)inv[(size_t)top->attached[(size_t)i]];
+    r = upload_target_bits(top, tgt, st);
+    if (r) return r;
+    const ReplayCSR csr = replay_csr(top);
+    const ReplayWs ws = replay_ws(top);
+    int chunk = ws.slots;
+    if (top->traceChunk > 0) chunk = std::min(chunk, top->traceChunk);
+    if (chunk < 1) return -3;
+    std::vector<uint32_t> rslot(nv);
+    size_t mmax = 0;
+    for (size_t q = 0; q < nv; q++) rslot[q] = rsi[q] % (uint32_t)chunk;
+    for (int s0 = 0; s0 < nsrc; s0 += chunk)
+        mmax = std::max<size_t>(mmax, srcStart[(size_t)std::min(nsrc, s0 + chunk)] - srcStart[(size_t)s0]);
+
+    DevBuf<uint32_t> d_srcs, d_rslot, d_rsrc, d_rdst, d_ridx;
+    DevBuf<TraceRoute> d_routes;
+    DevBuf<int64_t> d_gneed, d_goff, d_lneed, d_coff, d_loff;
+    DevBuf<unsigned long long> d_st;  // its own counters: the last build's stay intact
+    DevBuf<int32_t> d_outV, d_outE;
+    HIPCHK(d_srcs.ensure((size_t)nsrc));
+    HIPCHK(d_rslot.ensure(nv)); HIPCHK(d_rsrc.ensure(nv)); HIPCHK(d_rdst.ensure(nv));
+    HIPCHK(d_ridx.ensure(nv));
+    HIPCHK(d_routes.ensure((size_t)n));
+    HIPCHK(d_gneed.ensure((size_t)n + 1)); HIPCHK(d_goff.ensure((size_t)n + 1));
+    HIPCHK(d_lneed.ensure(mmax + 1)); HIPCHK(d_coff.ensure(mmax + 1)); HIPCHK(d_loff.ensure(nv));
+    HIPCHK(d_st.ensure(ST_COUNT));
+    HIPCHK(hipMemcpy(d_srcs.p, srcs.data(), 4 * (size_t)nsrc, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_rslot.p, rslot.data(), 4 * nv, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_rsrc.p, rsrc.data(), 4 * nv, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_rdst.p, rdst.data(), 4 * nv, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_ridx.p, order.data(), 4 * nv, hipMemcpyHostToDevice));
+    // requests with an unattached end keep their host image; pass 1 writes the others
+    for (int64_t i = 0; i < n; i++) routes[i] = route_blank(kTraceUnattached);
+    HIPCHK(hipMemcpy(d_routes.p, routes, sizeof(ShdRoute) * (size_t)n, hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(d_gneed.p, 0, 8 * ((size_t)n + 1), st));
+
+    TraceEvents ev;
+    for (hipEvent_t& x : ev.e) HIPCHK(hipEventCreate(&x));
+    const TraceIds ids{top->d_tperm.p, top->d_reid.p, top->d_selfEid.p};
+    std::vector<std::unique_ptr<DevBuf<int32_t>>> stage;  // per chunk: vertices, edges
+    auto reqs = [&](int s0, int s1) {
+        TraceReqs rq;
+        const size_t q0 = srcStart[(size_t)s0];
+        rq.n = (int64_t)(srcStart[(size_t)s1] - q0);
+        rq.rslot = d_rslot.p + q0;
+        rq.rsrc = d_rsrc.p + q0;
+        rq.rdst = d_rdst.p + q0;
+        rq.ridx = d_ridx.p + q0;
+        return rq;
+    };
+    float ms = 0;
+    for (int s0 = 0; s0 < nsrc; s0 += chunk) {
+        const int s1 = std::min(nsrc, s0 + chunk);
+        const TraceReqs rq = reqs(s0, s1);
+        const size_t q0 = srcStart[(size_t)s0], m = (size_t)rq.n;
+        HIPCHK(hipMemsetAsync(d_st.p, 0, sizeof(unsigned long long) * ST_COUNT, st));
+        HIPCHK(hipEventRecord(ev.e[0], st));
+        HIPCHK(launch_heap_replay_trace(csr, ws, d_srcs.p + s0, s1 - s0, d_st.p, st));
+        HIPCHK(hipEventRecord(ev.e[1], st));
+        HIPCHK(hipMemsetAsync(d_lneed.p, 0, 8 * (m + 1), st));
+        HIPCHK(launch_route_trace_count(csr, ws, rq, d_routes.p, d_lneed.p, d_gneed.p, st));
+        HIPCHK(trace_exclusive_scan(d_lneed.p, d_coff.p, (int64_t)m + 1, st));
+        int64_t tot = 0;
+        HIPCHK(hipMemcpy(&tot, d_coff.p + m, 8, hipMemcpyDeviceToHost));
+        stage.emplace_back(new DevBuf<int32_t>());
+        stage.emplace_back(new DevBuf<int32_t>());
+        DevBuf<int32_t>& stV = *stage[stage.size() - 2];
+        DevBuf<int32_t>& stE = *stage[stage.size() - 1];
+        HIPCHK(stV.ensure((size_t)std::max<int64_t>(1, tot)));
+        HIPCHK(stE.ensure((size_t)std::max<int64_t>(1, tot)));
+        HIPCHK(launch_route_trace_write(csr, ws, ids, rq, d_routes.p, d_coff.p, stV.p, stE.p, st));
+        HIPCHK(hipMemcpyAsync(d_loff.p + q0, d_coff.p, 8 * m, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipEventRecord(ev.e[2], st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+        ts->replay_ms += ms;
+        HIPCHK(hipEventElapsedTime(&ms, ev.e[1], ev.e[2]));
+        ts->trace_kernel_ms += ms;
+        ts->chunks++;
+    }
+
+    // the call's offsets: exclusive scan in request order, then the routes that fit are copied out
+    HIPCHK(hipEventRecord(ev.e[0], st));
+    HIPCHK(trace_exclusive_scan(d_gneed.p, d_goff.p, n + 1, st));
+    HIPCHK(launch_route_trace_place(n, d_routes.p, d_goff.p, cap, st));
+    int64_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, d_goff.p + n, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(routes, d_routes.p, sizeof(ShdRoute) * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    int64_t fit = 0;  // the placed routes fill [0, fit): offsets are a running sum
+    for (int64_t i = 0; i < n; i++)
+        if (routes[i].status == kTraceOk && routes[i].offset >= 0)
+            fit = std::max(fit, routes[i].offset + routes[i].hops + 1);
+    if (fit > cap) return -3;
+    if (fit > 0) {
+        HIPCHK(d_outV.ensure((size_t)fit));
+        HIPCHK(d_outE.ensure((size_t)fit));
+        size_t c = 0;
+        for (int s0 = 0; s0 < nsrc; s0 += chunk, c += 2)
+            HIPCHK(launch_route_trace_scatter(reqs(s0, std::min(nsrc, s0 + chunk)), d_routes.p,
+                                              d_loff.p + srcStart[(size_t)s0], stage[c]->p,
+                                              stage[c + 1]->p, d_outV.p, d_outE.p, st));
+    }
+    HIPCHK(hipEventRecord(ev.e[1], st));
+    if (fit > 0) {
+        HIPCHK(hipMemcpyAsync(vertices, d_outV.p, 4 * (size_t)fit, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(edges, d_outE.p, 4 * (size_t)fit, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+    ts->trace_kernel_ms += ms;
+    return total;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t shdtopo_trace_routes(Topology* top, const uint32_t* srcIP, const uint32_t* dstIP, int64_t n,
+                             ShdRoute* routes, int32_t* vertices, int32_t* edges, int64_t cap) {
+    if (!top || n < 0 || cap < 0 || n > 0x7FFFFFFE) return -1;
+    if (n > 0 && (!srcIP || !dstIP || !routes)) return -1;
+    if (cap > 0 && (!vertices || !edges)) return -1;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::lock_guard<std::mutex> lk(top->buildMu);
+    ShdTraceStats ts{};
+    ts.requests = n;
+    compute_geometry(top);
+    // both ends on a vertex of the current attached set (a table column), else status 1
+    std::vector<int32_t> sv((size_t)n), dv((size_t)n);
+    int64_t nvalid = 0;
+    for (int64_t i = 0; i < n; i++) {
+        int32_t s = vertex_of_ip(top, srcIP[i]), d = vertex_of_ip(top, dstIP[i]);
+        if (s >= 0 && (s >= top->g.V || top->colOf[(size_t)s] < 0)) s = -1;
+        if (d >= 0 && (d >= top->g.V || top->colOf[(size_t)d] < 0)) d = -1;
+        sv[(size_t)i] = s;
+        dv[(size_t)i] = d;
+        if (s >= 0 && d >= 0) nvalid++;
+    }
+    int64_t total = 0;
+    if (top->isComplete) {
+        total = trace_complete(top, sv, dv, n, routes, vertices, edges, cap);
+    } else if (nvalid == 0) {
+        for (int64_t i = 0; i < n; i++) routes[i] = route_blank(kTraceUnattached);
+    } else {
+        total = trace_replay(top, sv, dv, n, routes, vertices, edges, cap, &ts);
+    }
+    ts.entries = total;
+    ts.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    top->traceStats = ts;
+    return total;
+}
+
+int shdtopo_trace_stats(Topology* top, ShdTraceStats* out) {
+    if (!top || !out) return -1;
+    std::lock_guard<std::mutex> lk(top->buildMu);
+    *out = top->traceStats;
+    return 0;
+}
+
+int64_t shdtopo_format_route(Topology* top, const ShdRoute* r, const int32_t* vertices,
+                             const int32_t* edges, char* buf, size_t cap) {
+    if (!top || !r || !vertices || !edges || (cap > 0 && !buf)) return -1;
+    if (r->status != kTraceOk || r->offset < 0 || r->hops < 1) return -1;
+    const HostGraph& g = top->g;
+    const int32_t* v = vertices + r->offset;
+    const int32_t* e = edges + r->offset;
+    const int64_t h = r->hops;
+    for (int64_t k = 0; k <= h; k++)
+        if (v[k] < 0 || v[k] >= g.V) return -1;
+    for (int64_t k = 0; k < h; k++)
+        if (e[k] < 0 || (int64_t)e[k] >= g.E) return -1;
+    // shd-topology.c:594,644,654-656
+    char num[400];
+    std::string path = g.vid[(size_t)v[0]];
+    for (int64_t k = 0; k < h; k++) {
+        snprintf(num, sizeof num, "--[%f,%f]-->", g.elat[(size_t)e[k]], 1.0 - g.eloss[(size_t)e[k]]);
+        path += num;
+        path += g.vid[(size_t)v[k + 1]];
+    }
+    std::string out = "shortest path " + g.vid[(size_t)v[0]] + "-->" + g.vid[(size_t)v[h]];
+    snprintf(num, sizeof num, " (%i-->%i) is %f ms", (int)v[0], (int)v[h], r->latency);
+    out += num;
+    snprintf(num, sizeof num, " with %f loss, path: ", 1.0 - r->reliability);
+    out += num;
+    out += path;
+    if (cap > 0) {
+        const size_t c = std::min(out.size(), cap - 1);
+        memcpy(buf, out.data(), c);
+        buf[c] = 0;
+    }
+    return (int64_t)out.size();
 }
 
 int64_t shdtopo_export_csr(Topology* top, int32_t* perm, uint32_t* rowptr, uint32_t* col,

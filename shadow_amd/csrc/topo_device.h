@@ -312,6 +312,63 @@ hipError_t launch_heap_replay(const ReplayCSR& g, const ReplayWs& ws, const uint
 int replay_lds_levels(int int_keys);
 int replay_lds_bytes(int int_keys);  // LDS of one replay wavefront (its heap's top levels)
 
+// ---- route tracing (topo_trace.hip): the vertex / edge path behind a table entry ----
+// The replay's trace launch: block b replays d_sources[b] once in slot b (nrows <= ws.slots) with
+// the early exit on, writes no table row and leaves the slot's vertex records for the walk.
+hipError_t launch_heap_replay_trace(const ReplayCSR& g, const ReplayWs& ws,
+                                    const uint32_t* d_sources, int nrows,
+                                    unsigned long long* d_stats, hipStream_t stream);
+// one route's header: the device image of ShdRoute (include/shd_topology_abi.h)
+struct TraceRoute {
+    int64_t offset;
+    int32_t hops, status;
+    double latency, reliability;
+};
+enum { kTraceOk = 0, kTraceUnattached = 1, kTraceBroken = 2, kTraceCap = 3 };
+// ids the replay CSR does not carry (uploaded by the first trace): perm (relabelled -> original
+// vertex), eid (the igraph_get_eid edge -- lowest id of the parallel group -- of every replay-CSR
+// entry), selfEid (lowest-id self loop of every relabelled vertex, -1 = none)
+struct TraceIds {
+    const int32_t* perm = nullptr;
+    const int32_t* eid = nullptr;
+    const int32_t* selfEid = nullptr;
+};
+// eid[j] for every entry of the replay CSR from the parsed edges (document order = edge id)
+hipError_t launch_trace_edge_ids(int64_t V, int64_t E, int directed, const int32_t* eu,
+                                 const int32_t* ev, const uint32_t* inv, const int32_t* perm,
+                                 const uint32_t* rowptr, const uint4* rec, int64_t nadj,
+                                 int32_t* eid, hipStream_t stream);
+// The requests of one chunk of traced sources, sorted by source: request q has its source's
+// records in slot rslot[q], walks from rdst[q] back to rsrc[q] (relabelled ids) and belongs to
+// request ridx[q] of the call.
+struct TraceReqs {
+    int64_t n = 0;
+    const uint32_t* rslot = nullptr;
+    const uint32_t* rsrc = nullptr;
+    const uint32_t* rdst = nullptr;
+    const uint32_t* ridx = nullptr;
+};
+// Pass 1: hops and status of every request into routes[ridx]; the entries it needs (hops + 1,
+// 0 when not traced) into lneed[q] (chunk order) and gneed[ridx] (request order).
+hipError_t launch_route_trace_count(const ReplayCSR& g, const ReplayWs& ws, const TraceReqs& rq,
+                                    TraceRoute* routes, int64_t* lneed, int64_t* gneed,
+                                    hipStream_t stream);
+// Pass 2: vertices and edge ids, source first, at loff[q] of the chunk's staging arrays; latency
+// and reliability into routes[ridx].
+hipError_t launch_route_trace_write(const ReplayCSR& g, const ReplayWs& ws, const TraceIds& ids,
+                                    const TraceReqs& rq, TraceRoute* routes, const int64_t* loff,
+                                    int32_t* stV, int32_t* stE, hipStream_t stream);
+// out[i] = sum of in[0..i) for i < n (device exclusive scan)
+hipError_t trace_exclusive_scan(const int64_t* in, int64_t* out, int64_t n, hipStream_t stream);
+// offsets of the call: routes[i].offset = goff[i] when the route fits below cap entirely, else
+// offset -1 and status kTraceCap (traced routes only)
+hipError_t launch_route_trace_place(int64_t n, TraceRoute* routes, const int64_t* goff,
+                                    int64_t cap, hipStream_t stream);
+// copy the placed routes of a chunk from its staging arrays to outV / outE at their offsets
+hipError_t launch_route_trace_scatter(const TraceReqs& rq, const TraceRoute* routes,
+                                      const int64_t* loff, const int32_t* stV, const int32_t* stE,
+                                      int32_t* outV, int32_t* outE, hipStream_t stream);
+
 hipError_t launch_pair_table_complete(int A, int64_t row0, int64_t rows, const double* elatAA,
                                       const double* elossAA, const double* vlossA, double2* out_lr,
                                       uint16_t* out_hops, double* out_rowmin,

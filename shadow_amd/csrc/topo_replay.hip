@@ -554,7 +554,10 @@ __device__ __forceinline__ uint32_t vr_par(const uint4* vr, uint32_t v) { return
 #ifndef SHD_RP_WAVES_EU
 #define SHD_RP_WAVES_EU 4  // minimum waves per SIMD the register allocation must allow
 #endif
-template <bool I>
+// TR (route tracing, topo_trace.hip): block b replays row b once in slot b and stops -- no
+// dequeue, no per-target helper -- so every traced source's vertex records stay in a known slot
+// for route_trace_kernel.  Table builds run the TR = false instantiations.
+template <bool I, bool TR = false>
 __global__ void __launch_bounds__(64, SHD_RP_WAVES_EU)
 heap_replay_kernel(ReplayCSR g, ReplayWs ws, const uint32_t* __restrict__ sources,
                    const uint32_t* __restrict__ rows, int nrows,
@@ -580,10 +583,15 @@ heap_replay_kernel(ReplayCSR g, ReplayWs ws, const uint32_t* __restrict__ source
 
     for (;;) {
         uint32_t item = 0;
-        if (lane == 0) item = (uint32_t)atomicAdd(&stats[ST_RP_DEQUEUE], 1ull);
-        item = rl_u32(item, 0);
+        if constexpr (TR) {
+            if (n_rows) break;
+            item = blockIdx.x;
+        } else {
+            if (lane == 0) item = (uint32_t)atomicAdd(&stats[ST_RP_DEQUEUE], 1ull);
+            item = rl_u32(item, 0);
+        }
         if (item >= (uint32_t)nrows) break;
-        const uint32_t row = rows[item];
+        const uint32_t row = TR ? item : rows[item];
         const uint32_t src = uni_u32(sources[row]);
         n_rows++;
 
@@ -753,6 +761,7 @@ heap_replay_kernel(ReplayCSR g, ReplayWs ws, const uint32_t* __restrict__ source
             }
         }
 
+        if constexpr (TR) continue;  // the routes are walked by route_trace_kernel
         // ---- per-target helper (shd-topology.c:561-671) ----
         double rmin = INFINITY;
         const size_t rowbase = (size_t)row * (size_t)A;
@@ -875,6 +884,22 @@ hipError_t launch_heap_replay(const ReplayCSR& g, const ReplayWs& ws, const uint
         hipLaunchKernelGGL(heap_replay_kernel<false>, dim3(grid), dim3(64), 0, stream, g, ws,
                            d_sources, d_rows, nrows, d_targets, A, full, out_lr, out_hops,
                            out_rowmin, d_stats, dbg_dist, dbg_par);
+    return hipGetLastError();
+}
+
+hipError_t launch_heap_replay_trace(const ReplayCSR& g, const ReplayWs& ws,
+                                    const uint32_t* d_sources, int nrows,
+                                    unsigned long long* d_stats, hipStream_t stream) {
+    if (nrows < 1) return hipSuccess;
+    if (g.V <= 0 || nrows > ws.slots) return hipErrorInvalidValue;
+    if (g.intKeys)
+        hipLaunchKernelGGL((heap_replay_kernel<true, true>), dim3(nrows), dim3(64), 0, stream, g,
+                           ws, d_sources, nullptr, nrows, nullptr, 0, 0, nullptr, nullptr, nullptr,
+                           d_stats, nullptr, nullptr);
+    else
+        hipLaunchKernelGGL((heap_replay_kernel<false, true>), dim3(nrows), dim3(64), 0, stream, g,
+                           ws, d_sources, nullptr, nrows, nullptr, 0, 0, nullptr, nullptr, nullptr,
+                           d_stats, nullptr, nullptr);
     return hipGetLastError();
 }
 

@@ -310,6 +310,63 @@ class Topology:
             raise RuntimeError("shdtopo_replay_source failed: %d" % r)
         return dist, par
 
+    # ---- route tracing ----
+    def trace_routes(self, src_ips, dst_ips, cap=None):
+        """shdtopo_trace_routes: the vertex / edge route of every (src, dst) host pair, the
+        forward route of the source's table row.  Returns a dict of numpy arrays: per request
+        ``offset, hops, status, latency, reliability`` and the concatenated ``vertices, edges``
+        (route i = entries [offset, offset + hops]; edges[offset + hops] = -1), plus ``total``,
+        the entries every route needs.  cap=None sizes the buffers first (a cap = 0 call); a
+        smaller cap writes only the routes that fit (the others: status 3, offset -1)."""
+        s = np.ascontiguousarray(src_ips, dtype=np.uint32)
+        d = np.ascontiguousarray(dst_ips, dtype=np.uint32)
+        if s.shape != d.shape or s.ndim != 1:
+            raise ValueError("src_ips and dst_ips must be 1-D and of one length")
+        n = len(s)
+        routes = (L.ShdRoute * max(n, 1))()
+        if cap is None:
+            cap = int(self._lib.shdtopo_trace_routes(self._h, _p(s), _p(d), n, routes, None,
+                                                     None, 0))
+            if cap < 0:
+                raise RuntimeError("shdtopo_trace_routes failed: %d" % cap)
+        cap = int(cap)
+        vertices = np.full(max(cap, 1), -2, np.int32)
+        edges = np.full(max(cap, 1), -2, np.int32)
+        total = int(self._lib.shdtopo_trace_routes(self._h, _p(s), _p(d), n, routes,
+                                                   _p(vertices) if cap else None,
+                                                   _p(edges) if cap else None, cap))
+        if total < 0:
+            raise RuntimeError("shdtopo_trace_routes failed: %d" % total)
+        r = np.frombuffer(routes, dtype=np.dtype(
+            [("offset", np.int64), ("hops", np.int32), ("status", np.int32),
+             ("latency", np.float64), ("reliability", np.float64)]), count=n)
+        out = {k: r[k].copy() for k in ("offset", "hops", "status", "latency", "reliability")}
+        out["vertices"] = vertices[:cap]
+        out["edges"] = edges[:cap]
+        out["total"] = total
+        return out
+
+    def format_route(self, trace, i):
+        """shdtopo_format_route: the reference's debug line (shd-topology.c:654-656, the text after
+        ``debug(``) for request i of a trace_routes result."""
+        r = L.ShdRoute(int(trace["offset"][i]), int(trace["hops"][i]), int(trace["status"][i]),
+                       float(trace["latency"][i]), float(trace["reliability"][i]))
+        v = np.ascontiguousarray(trace["vertices"], dtype=np.int32)
+        e = np.ascontiguousarray(trace["edges"], dtype=np.int32)
+        n = int(self._lib.shdtopo_format_route(self._h, ctypes.byref(r), _p(v), _p(e), None, 0))
+        if n < 0:
+            raise RuntimeError("shdtopo_format_route failed: %d" % n)
+        buf = ctypes.create_string_buffer(n + 1)
+        self._lib.shdtopo_format_route(self._h, ctypes.byref(r), _p(v), _p(e), buf, n + 1)
+        return buf.value.decode()
+
+    def trace_stats(self):
+        """The last trace's own counters (shdtopo_trace_stats)."""
+        s = L.ShdTraceStats()
+        if self._lib.shdtopo_trace_stats(self._h, ctypes.byref(s)) != 0:
+            raise RuntimeError("shdtopo_trace_stats failed")
+        return {k: getattr(s, k) for k, _ in L.ShdTraceStats._fields_}
+
     def write_graphml(self, path):
         if self._lib.shdtopo_write_graphml(self._h, path.encode()) != 0:
             raise RuntimeError("write_graphml failed")
