@@ -134,7 +134,11 @@ Topology* shdtopo_new_from_buffer(const char* graphml, size_t len);
  * batches are sized (one round of the slots) or dequeued longest first (several rounds) by the
  * sources' costs measured from the earlier builds' batch times; 0: the grouping order only),
  * "trace_chunk" (sources per replay launch of shdtopo_trace_routes; 0, the default: the replay's
- * wavefront slots; a small value forces several chunks -- a test hook).
+ * wavefront slots; a small value forces several chunks -- a test hook; it bounds
+ * shdtopo_link_load's launches too), "load_walk" (shdtopo_link_load: 1, the default, walks every
+ * request's route with two atomics per hop; 0 sums the weights leaf to root over each source's
+ * tree of requested routes, one add per tree vertex -- measured no faster at the bench size,
+ * DESIGN.md 3.7; both give the same sums; any other value is rejected).
  * Returns 0 or -1 for an unknown key / bad value. */
 int shdtopo_set_option(Topology* top, const char* key, double value);
 
@@ -476,6 +480,57 @@ typedef struct {
     int64_t entries;        /* the call's return value */
 } ShdTraceStats;
 int shdtopo_trace_stats(Topology* top, ShdTraceStats* out);
+
+/* ---- link load: per-edge and per-vertex traffic of a set of flows ----
+ * "Which links carry my traffic": for n flows (source host, destination host, weight; IPs in
+ * network order, duplicates and any order are fine) the weight that crosses every edge and arrives
+ * at every vertex.  Route i is exactly the route shdtopo_trace_routes reports for
+ * (srcIP[i], dstIP[i]): the forward route of the source's row for the current attached set, each
+ * hop over the igraph_get_eid edge (the lowest id of a parallel group), the self loop for two
+ * hosts on one vertex or src == dst.
+ *
+ * For every hop from vertex a to vertex b over edge e (ids in document order):
+ *   edgeLoad[e] += w       when a == eu[e]: the forward half -- also every self loop and every
+ *                          arc of a directed topology;
+ *   edgeLoad[E + e] += w   otherwise: the reverse half (all zero on a directed topology);
+ *   vertexLoad[b] += w     the weight arriving at b (original vertex ids): every vertex of the
+ *                          route but its first; a self pair arrives once, over its loop.
+ * weight = NULL counts 1 per flow (packets); weight = payloadLength gives bytes.  Sums are
+ * unsigned 64-bit and wrap, so they do not depend on request order, chunking or scheduling.
+ * edgeLoad (u64[2 E]) and vertexLoad (u64[V]) are overwritten, not accumulated into; either may
+ * be NULL.  Requests with an unattached end, and unroutable ones (a broken chain, a self pair
+ * without a self loop), are counted in the statistics and skipped.  Returns the number of flows
+ * that contributed, or a negative error (-1: bad arguments -- NULL top, n < 0, a NULL IP array
+ * with n > 0).
+ *
+ * SSSP topologies: the distinct sources run through the exact heap replay in chunks (option
+ * "trace_chunk"), as a trace; the accumulation itself is microseconds to milliseconds next to it
+ * (option "load_walk" selects between the per-request walk and the tree sums).  Complete topologies are
+ * answered on the host from the parsed graph: no device is used.  A multi-device topology runs on
+ * its first device.  Like a trace, the call materialises no lazy row, pushes no minimum, neither
+ * invalidates nor rebuilds the table and leaves ShdStats as it was. */
+typedef struct {
+    double  total_ms;        /* wall time of the call */
+    double  replay_ms;       /* event time of its heap-replay launches */
+    double  load_kernel_ms;  /* event time of the accumulation kernels (everything but the replay) */
+    double  ids_ms;          /* edge-id upload, first trace/load of a topology, else 0 */
+    int64_t requests;        /* n */
+    int64_t routed;          /* requests that contributed */
+    int64_t unattached;      /* requests with an unattached end (contribute nothing) */
+    int64_t broken;          /* unroutable / broken chain / self pair without a self loop */
+    int64_t sources;         /* distinct source vertices replayed */
+    int64_t chunks;          /* replay launches */
+    int64_t tree_vertices;   /* sum over sources of the vertices in the union of its requested chains
+                                (the source aside: = adds into the edge accumulators, self pairs
+                                apart); 0 for the per-request walk */
+    uint64_t hop_weight;     /* sum over routed requests of weight x hops (= sum of edgeLoad) */
+} ShdLoadStats;
+
+int64_t shdtopo_link_load(Topology* top, const uint32_t* srcIP, const uint32_t* dstIP,
+                          const uint64_t* weight /* NULL: 1 each */, int64_t n,
+                          uint64_t* edgeLoad /* u64[2 * E], may be NULL */,
+                          uint64_t* vertexLoad /* u64[V], may be NULL */);
+int shdtopo_link_load_stats(Topology* top, ShdLoadStats* out);
 
 /* Test hook: the device graph preparation (topo_prep.hip) read back -- perm
  * int32[V] (relabelled -> original vertex), rowptr u32[V+1], the adjacency columns u32[2E']

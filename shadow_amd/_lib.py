@@ -74,6 +74,12 @@ class ShdTraceStats(ctypes.Structure):
                 ("requests", i64), ("sources", i64), ("chunks", i64), ("entries", i64)]
 
 
+class ShdLoadStats(ctypes.Structure):
+    _fields_ = [("total_ms", dbl), ("replay_ms", dbl), ("load_kernel_ms", dbl), ("ids_ms", dbl),
+                ("requests", i64), ("routed", i64), ("unattached", i64), ("broken", i64),
+                ("sources", i64), ("chunks", i64), ("tree_vertices", i64), ("hop_weight", u64)]
+
+
 class ShdSynthParams(ctypes.Structure):
     _fields_ = [("seed", u64), ("n_routers", i64), ("n_poi", i64), ("n_edges", i64),
                 ("integer_latency", ctypes.c_int), ("alpha", dbl), ("directed", ctypes.c_int)]
@@ -128,6 +134,8 @@ SIGNATURES = {
     "shdtopo_trace_routes": (i64, [P, P, P, i64, P, P, P, i64]),
     "shdtopo_format_route": (i64, [P, P, P, P, P, ctypes.c_size_t]),
     "shdtopo_trace_stats": (ctypes.c_int, [P, P]),
+    "shdtopo_link_load": (i64, [P, P, P, P, i64, P, P]),
+    "shdtopo_link_load_stats": (ctypes.c_int, [P, P]),
     "shdtopo_test_segsort": (ctypes.c_int, [P, i64, P, i64, ctypes.c_int, P, P]),
     "shdtopo_test_batch_layout": (ctypes.c_int, [P, i64, dbl, ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_int, P, P, P]),

@@ -453,6 +453,10 @@ struct _Topology {
     bool traceIdsReady = false;
     DevBuf<int32_t> d_tperm, d_reid, d_selfEid;
     ShdTraceStats traceStats{};  // the last trace's own counters
+    // link load (shdtopo_link_load, topo_load.hip)
+    int loadWalk = 1;            // option "load_walk": 1 = the per-request walk (the default:
+                                 // DESIGN.md 3.7), 0 = the leaf-to-root tree accumulation
+    ShdLoadStats loadStats{};    // the last call's own counters
 
     // multi-GPU build inside the library (one Shadow process): device d builds
     // rows [d*R, (d+1)*R) with its own stream / workspace (a peer Topology on that device),
@@ -3383,6 +3387,10 @@ int shdtopo_set_option(Topology* top, const char* key, double value) {
         if (!(value >= 0 && value <= 1e9)) return -1;
         top->traceChunk = (int)value;
     }
+    else if (k == "load_walk") {
+        if (value != 0 && value != 1) return -1;
+        top->loadWalk = (int)value;
+    }
     else if (k == "tie_dense") top->tieDenseOpt = value < 0 ? -1 : (value != 0 ? 1 : 0);
     else if (k == "source_order") top->sourceOrder = (int)value;
     else if (k == "batch_order") top->batchOrder = (int)value;
@@ -4077,8 +4085,9 @@ int64_t place_routes_host(ShdRoute* routes, int64_t n, int64_t cap) {
 
 // _topology_lookupPath (shd-topology.c:835-873) with its route: one hop over the igraph_get_eid
 // edge (lowest id) of the pair, the self loop for a self pair.  Host only: the parsed graph.
-int64_t trace_complete(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
-                       int64_t n, ShdRoute* routes, int32_t* vertices, int32_t* edges, int64_t cap) {
+// the igraph_get_eid edge (lowest id; -1 = none) of every (sv[i], dv[i]) with both ends attached
+std::vector<int32_t> complete_pair_eids(Topology* top, const std::vector<int32_t>& sv,
+                                        const std::vector<int32_t>& dv, int64_t n) {
     const HostGraph& g = top->g;
     auto key = [](int32_t a, int32_t b) { return ((uint64_t)(uint32_t)a << 32) | (uint32_t)b; };
     std::unordered_map<uint64_t, int32_t> eidOf;
@@ -4093,6 +4102,16 @@ int64_t trace_complete(Topology* top, const std::vector<int32_t>& sv, const std:
             if (it != eidOf.end() && it->second < 0) it->second = (int32_t)e;
         }
     }
+    std::vector<int32_t> pe((size_t)n, -1);
+    for (int64_t i = 0; i < n; i++)
+        if (sv[(size_t)i] >= 0 && dv[(size_t)i] >= 0) pe[(size_t)i] = eidOf[key(sv[(size_t)i], dv[(size_t)i])];
+    return pe;
+}
+
+int64_t trace_complete(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
+                       int64_t n, ShdRoute* routes, int32_t* vertices, int32_t* edges, int64_t cap) {
+    const HostGraph& g = top->g;
+    const std::vector<int32_t> pe = complete_pair_eids(top, sv, dv, n);
     std::vector<int32_t> eids((size_t)n, -1);
     for (int64_t i = 0; i < n; i++) {
         const int32_t s = sv[(size_t)i], d = dv[(size_t)i];
@@ -4100,7 +4119,7 @@ int64_t trace_complete(Topology* top, const std::vector<int32_t>& sv, const std:
             routes[i] = route_blank(kTraceUnattached);
             continue;
         }
-        const int32_t e = eidOf[key(s, d)];
+        const int32_t e = pe[(size_t)i];
         if (e < 0) {  // igraph_get_eid fails (shd-topology.c:857)
             routes[i] = route_blank(kTraceBroken);
             continue;
@@ -4178,33 +4197,62 @@ struct TraceEvents {
     }
 };
 
-// SSSP topologies: replay the distinct sources in chunks, walk the requests' chains (topo_trace.hip)
-int64_t trace_replay(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
-                     int64_t n, ShdRoute* routes, int32_t* vertices, int32_t* edges, int64_t cap,
-                     ShdTraceStats* ts) {
+// The requests of a trace or a link load grouped for the replay: those with both ends attached,
+// sorted by source (stable: request order within a source), a CSR over the distinct sources and
+// each source's slot within its chunk, uploaded; the replay's CSR and workspace for the table
+// build's target set; the events that time a chunk.
+struct ReplayReqs {
+    std::unique_ptr<TraceKeep> keep;  // declared first: ShdStats and the launch width go back last
+    std::vector<uint32_t> order, srcs, srcStart;
+    size_t nv = 0, mmax = 0;  // grouped requests; the most of one chunk
+    int nsrc = 0, chunk = 0;
+    ReplayCSR csr;
+    ReplayWs ws;
+    TraceIds ids;
+    DevBuf<uint32_t> d_srcs, d_rslot, d_rsrc, d_rdst, d_ridx;
+    DevBuf<unsigned long long> d_st;  // its own counters: the last build's stay intact
+    TraceEvents ev;
+    TraceReqs reqs(int s0, int s1) const {
+        TraceReqs rq;
+        const size_t q0 = srcStart[(size_t)s0];
+        rq.n = (int64_t)(srcStart[(size_t)s1] - q0);
+        rq.rslot = d_rslot.p + q0;
+        rq.rsrc = d_rsrc.p + q0;
+        rq.rdst = d_rdst.p + q0;
+        rq.ridx = d_ridx.p + q0;
+        return rq;
+    }
+};
+
+// sv / dv: the requests' vertices (-1 = not attached).  Prepares the device, the replay and the
+// edge ids (*ids_ms), and fills R.
+int group_replay_requests(Topology* top, const std::vector<int32_t>& sv,
+                          const std::vector<int32_t>& dv, int64_t n, double* ids_ms,
+                          ReplayReqs& R) {
     int r = dev_init(top);
     if (r) return r;
     r = collect_row_stats(top);  // the last build's counters are read before the replay is reused
     if (r) return r;
-    TraceKeep keep(top);
+    R.keep.reset(new TraceKeep(top));
     r = upload_csr(top);
     if (r) return r;
     r = upload_replay(top);
     if (r) return r;
-    r = ensure_trace_ids(top, &ts->ids_ms);
+    r = ensure_trace_ids(top, ids_ms);
     if (r) return r;
     hipStream_t st = top->stream;
     const std::vector<int32_t>& inv = top->hp->inv;
 
-    // requests sorted by source (stable: request order within a source), CSR over the sources
-    std::vector<uint32_t> order;
+    std::vector<uint32_t>& order = R.order;
     for (int64_t i = 0; i < n; i++)
         if (sv[(size_t)i] >= 0 && dv[(size_t)i] >= 0) order.push_back((uint32_t)i);
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
         return inv[(size_t)sv[a]] < inv[(size_t)sv[b]];
     });
-    const size_t nv = order.size();
-    std::vector<uint32_t> srcs, srcStart, rsi(nv), rsrc(nv), rdst(nv);
+    const size_t nv = R.nv = order.size();
+    std::vector<uint32_t>& srcs = R.srcs;
+    std::vector<uint32_t>& srcStart = R.srcStart;
+    std::vector<uint32_t> rsi(nv), rsrc(nv), rdst(nv);
     for (size_t q = 0; q < nv; q++) {
         const uint32_t s = (uint32_t)inv[(size_t)sv[order[q]]];
         if (srcs.empty() || srcs.back() != s) {
@@ -4216,8 +4264,7 @@ int64_t trace_replay(Topology* top, const std::vector<int32_t>& sv, const std::v
         rdst[q] = (uint32_t)inv[(size_t)dv[order[q]]];
     }
     srcStart.push_back((uint32_t)nv);
-    const int nsrc = (int)srcs.size();
-    ts->sources = nsrc;
+    const int nsrc = R.nsrc = (int)srcs.size();
 
     // the table build's target set: the chains are the table's chains
     r = ensure_replay_ws(top, nsrc);
@@ -4227,62 +4274,79 @@ int64_t trace_replay(Topology* top, const std::vector<int32_t>& sv, const std::v
     for (int64_t i = 0; i < A; i++) tgt[(size_t)i] = (uint32_t)inv[(size_t)top->attached[(size_t)i]];
     r = upload_target_bits(top, tgt, st);
     if (r) return r;
-    const ReplayCSR csr = replay_csr(top);
-    const ReplayWs ws = replay_ws(top);
-    int chunk = ws.slots;
+    R.csr = replay_csr(top);
+    R.ws = replay_ws(top);
+    int chunk = R.ws.slots;
     if (top->traceChunk > 0) chunk = std::min(chunk, top->traceChunk);
     if (chunk < 1) return -3;
+    R.chunk = chunk;
     std::vector<uint32_t> rslot(nv);
-    size_t mmax = 0;
     for (size_t q = 0; q < nv; q++) rslot[q] = rsi[q] % (uint32_t)chunk;
     for (int s0 = 0; s0 < nsrc; s0 += chunk)
-        mmax = std::max<size_t>(mmax, srcStart[(size_t)std::min(nsrc, s0 + chunk)] - srcStart[(size_t)s0]);
+        R.mmax = std::max<size_t>(R.mmax, srcStart[(size_t)std::min(nsrc, s0 + chunk)] - srcStart[(size_t)s0]);
 
-    DevBuf<uint32_t> d_srcs, d_rslot, d_rsrc, d_rdst, d_ridx;
+    HIPCHK(R.d_srcs.ensure((size_t)nsrc));
+    HIPCHK(R.d_rslot.ensure(nv)); HIPCHK(R.d_rsrc.ensure(nv)); HIPCHK(R.d_rdst.ensure(nv));
+    HIPCHK(R.d_ridx.ensure(nv));
+    HIPCHK(R.d_st.ensure(ST_COUNT));
+    HIPCHK(hipMemcpy(R.d_srcs.p, srcs.data(), 4 * (size_t)nsrc, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(R.d_rslot.p, rslot.data(), 4 * nv, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(R.d_rsrc.p, rsrc.data(), 4 * nv, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(R.d_rdst.p, rdst.data(), 4 * nv, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(R.d_ridx.p, order.data(), 4 * nv, hipMemcpyHostToDevice));
+    for (hipEvent_t& x : R.ev.e) HIPCHK(hipEventCreate(&x));
+    R.ids = TraceIds{top->d_tperm.p, top->d_reid.p, top->d_selfEid.p};
+    return 0;
+}
+
+// Sources [s0, s1) of R replayed in slots 0 .. s1 - s0 - 1 (the trace launch: the vertex records
+// stay for the walks); R.ev.e[0] and e[1] bracket the launch.
+int launch_replay_chunk(Topology* top, ReplayReqs& R, int s0, int s1) {
+    hipStream_t st = top->stream;
+    HIPCHK(hipMemsetAsync(R.d_st.p, 0, sizeof(unsigned long long) * ST_COUNT, st));
+    HIPCHK(hipEventRecord(R.ev.e[0], st));
+    HIPCHK(launch_heap_replay_trace(R.csr, R.ws, R.d_srcs.p + s0, s1 - s0, R.d_st.p, st));
+    HIPCHK(hipEventRecord(R.ev.e[1], st));
+    return 0;
+}
+
+// SSSP topologies: replay the distinct sources in chunks, walk the requests' chains (topo_trace.hip)
+int64_t trace_replay(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
+                     int64_t n, ShdRoute* routes, int32_t* vertices, int32_t* edges, int64_t cap,
+                     ShdTraceStats* ts) {
+    ReplayReqs R;
+    int r = group_replay_requests(top, sv, dv, n, &ts->ids_ms, R);
+    if (r) return r;
+    hipStream_t st = top->stream;
+    const std::vector<uint32_t>& srcStart = R.srcStart;
+    const size_t nv = R.nv, mmax = R.mmax;
+    const int nsrc = R.nsrc, chunk = R.chunk;
+    const ReplayCSR& csr = R.csr;
+    const ReplayWs& ws = R.ws;
+    const TraceIds& ids = R.ids;
+    TraceEvents& ev = R.ev;
+    ts->sources = nsrc;
+
     DevBuf<TraceRoute> d_routes;
     DevBuf<int64_t> d_gneed, d_goff, d_lneed, d_coff, d_loff;
-    DevBuf<unsigned long long> d_st;  // its own counters: the last build's stay intact
     DevBuf<int32_t> d_outV, d_outE;
-    HIPCHK(d_srcs.ensure((size_t)nsrc));
-    HIPCHK(d_rslot.ensure(nv)); HIPCHK(d_rsrc.ensure(nv)); HIPCHK(d_rdst.ensure(nv));
-    HIPCHK(d_ridx.ensure(nv));
     HIPCHK(d_routes.ensure((size_t)n));
     HIPCHK(d_gneed.ensure((size_t)n + 1)); HIPCHK(d_goff.ensure((size_t)n + 1));
     HIPCHK(d_lneed.ensure(mmax + 1)); HIPCHK(d_coff.ensure(mmax + 1)); HIPCHK(d_loff.ensure(nv));
-    HIPCHK(d_st.ensure(ST_COUNT));
-    HIPCHK(hipMemcpy(d_srcs.p, srcs.data(), 4 * (size_t)nsrc, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_rslot.p, rslot.data(), 4 * nv, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_rsrc.p, rsrc.data(), 4 * nv, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_rdst.p, rdst.data(), 4 * nv, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_ridx.p, order.data(), 4 * nv, hipMemcpyHostToDevice));
     // requests with an unattached end keep their host image; pass 1 writes the others
     for (int64_t i = 0; i < n; i++) routes[i] = route_blank(kTraceUnattached);
     HIPCHK(hipMemcpy(d_routes.p, routes, sizeof(ShdRoute) * (size_t)n, hipMemcpyHostToDevice));
     HIPCHK(hipMemsetAsync(d_gneed.p, 0, 8 * ((size_t)n + 1), st));
 
-    TraceEvents ev;
-    for (hipEvent_t& x : ev.e) HIPCHK(hipEventCreate(&x));
-    const TraceIds ids{top->d_tperm.p, top->d_reid.p, top->d_selfEid.p};
+    auto reqs = [&](int s0, int s1) { return R.reqs(s0, s1); };
     std::vector<std::unique_ptr<DevBuf<int32_t>>> stage;  // per chunk: vertices, edges
-    auto reqs = [&](int s0, int s1) {
-        TraceReqs rq;
-        const size_t q0 = srcStart[(size_t)s0];
-        rq.n = (int64_t)(srcStart[(size_t)s1] - q0);
-        rq.rslot = d_rslot.p + q0;
-        rq.rsrc = d_rsrc.p + q0;
-        rq.rdst = d_rdst.p + q0;
-        rq.ridx = d_ridx.p + q0;
-        return rq;
-    };
     float ms = 0;
     for (int s0 = 0; s0 < nsrc; s0 += chunk) {
         const int s1 = std::min(nsrc, s0 + chunk);
         const TraceReqs rq = reqs(s0, s1);
         const size_t q0 = srcStart[(size_t)s0], m = (size_t)rq.n;
-        HIPCHK(hipMemsetAsync(d_st.p, 0, sizeof(unsigned long long) * ST_COUNT, st));
-        HIPCHK(hipEventRecord(ev.e[0], st));
-        HIPCHK(launch_heap_replay_trace(csr, ws, d_srcs.p + s0, s1 - s0, d_st.p, st));
-        HIPCHK(hipEventRecord(ev.e[1], st));
+        r = launch_replay_chunk(top, R, s0, s1);
+        if (r) return r;
         HIPCHK(hipMemsetAsync(d_lneed.p, 0, 8 * (m + 1), st));
         HIPCHK(launch_route_trace_count(csr, ws, rq, d_routes.p, d_lneed.p, d_gneed.p, st));
         HIPCHK(trace_exclusive_scan(d_lneed.p, d_coff.p, (int64_t)m + 1, st));
@@ -4338,6 +4402,108 @@ int64_t trace_replay(Topology* top, const std::vector<int32_t>& sv, const std::v
     return total;
 }
 
+// ---------------------------------------------------------------------------------------------
+// link load (include/shd_topology_abi.h shdtopo_link_load; kernels in topo_load.hip)
+// ---------------------------------------------------------------------------------------------
+// Complete topologies, on the host as trace_complete: one hop over the direct edge, a self pair
+// over the loop.
+int64_t load_complete(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
+                      const uint64_t* weight, int64_t n, uint64_t* edgeLoad, uint64_t* vertexLoad,
+                      ShdLoadStats* ls) {
+    const HostGraph& g = top->g;
+    const std::vector<int32_t> pe = complete_pair_eids(top, sv, dv, n);
+    for (int64_t i = 0; i < n; i++) {
+        const int32_t s = sv[(size_t)i], d = dv[(size_t)i];
+        if (s < 0 || d < 0) continue;  // counted by the caller
+        const int32_t e = pe[(size_t)i];
+        if (e < 0) {
+            ls->broken++;
+            continue;
+        }
+        const uint64_t w = weight ? weight[i] : 1;
+        if (edgeLoad) edgeLoad[s == g.eu[(size_t)e] ? (int64_t)e : g.E + e] += w;
+        if (vertexLoad) vertexLoad[d] += w;
+        ls->routed++;
+        ls->hop_weight += w;
+    }
+    return ls->routed;
+}
+
+// SSSP topologies: replay the distinct sources in chunks and accumulate along the chains
+int64_t load_replay(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
+                    const uint64_t* weight, int64_t n, uint64_t* edgeLoad, uint64_t* vertexLoad,
+                    ShdLoadStats* ls) {
+    ReplayReqs R;
+    int r = group_replay_requests(top, sv, dv, n, &ls->ids_ms, R);
+    if (r) return r;
+    hipStream_t st = top->stream;
+    const size_t nv = R.nv, V = (size_t)top->g.V, E = (size_t)top->g.E;
+    ls->sources = R.nsrc;
+
+    std::vector<unsigned long long> rw(nv, 1ull);
+    if (weight)
+        for (size_t q = 0; q < nv; q++) rw[q] = weight[R.order[q]];
+    DevBuf<unsigned long long> d_w, d_eload, d_vload, d_vout, d_cnt;
+    DevBuf<int32_t> d_hops;
+    HIPCHK(d_w.ensure(nv));
+    HIPCHK(d_hops.ensure(nv));
+    HIPCHK(d_eload.ensure(2 * E));
+    HIPCHK(d_vload.ensure(V));
+    HIPCHK(d_vout.ensure(V));
+    HIPCHK(d_cnt.ensure(LD_COUNT));
+    HIPCHK(hipMemcpy(d_w.p, rw.data(), 8 * nv, hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(d_eload.p, 0, 8 * std::max<size_t>(1, 2 * E), st));
+    HIPCHK(hipMemsetAsync(d_vload.p, 0, 8 * std::max<size_t>(1, V), st));
+    HIPCHK(hipMemsetAsync(d_vout.p, 0, 8 * std::max<size_t>(1, V), st));
+    HIPCHK(hipMemsetAsync(d_cnt.p, 0, 8 * LD_COUNT, st));
+    LoadAcc acc;
+    acc.eload = d_eload.p;
+    acc.vload = d_vload.p;
+    acc.E = (int64_t)E;
+    acc.eu = top->d_eu.p;
+
+    float ms = 0;
+    for (int s0 = 0; s0 < R.nsrc; s0 += R.chunk) {
+        const int s1 = std::min(R.nsrc, s0 + R.chunk);
+        const TraceReqs rq = R.reqs(s0, s1);
+        const size_t q0 = R.srcStart[(size_t)s0];
+        r = launch_replay_chunk(top, R, s0, s1);
+        if (r) return r;
+        HIPCHK(launch_load_validate(R.csr, R.ws, rq, d_w.p + q0, d_hops.p + q0, d_cnt.p, st));
+        if (top->loadWalk) {
+            HIPCHK(launch_load_walk(R.csr, R.ws, R.ids, rq, d_w.p + q0, d_hops.p + q0, acc, st));
+        } else {
+            HIPCHK(launch_load_reset(R.csr, R.ws, s1 - s0, st));
+            HIPCHK(launch_load_claim(R.csr, R.ws, R.ids, rq, d_w.p + q0, d_hops.p + q0, acc,
+                                     d_cnt.p, st));
+            HIPCHK(launch_load_push(R.csr, R.ws, R.ids, rq, d_hops.p + q0, acc, st));
+        }
+        HIPCHK(hipEventRecord(R.ev.e[2], st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipEventElapsedTime(&ms, R.ev.e[0], R.ev.e[1]));
+        ls->replay_ms += ms;
+        HIPCHK(hipEventElapsedTime(&ms, R.ev.e[1], R.ev.e[2]));
+        ls->load_kernel_ms += ms;
+        ls->chunks++;
+    }
+
+    HIPCHK(hipEventRecord(R.ev.e[0], st));
+    HIPCHK(launch_load_permute((int64_t)V, R.ids.perm, d_vload.p, d_vout.p, st));
+    HIPCHK(hipEventRecord(R.ev.e[1], st));
+    unsigned long long cnt[LD_COUNT] = {};
+    HIPCHK(hipMemcpyAsync(cnt, d_cnt.p, 8 * LD_COUNT, hipMemcpyDeviceToHost, st));
+    if (edgeLoad && E) HIPCHK(hipMemcpyAsync(edgeLoad, d_eload.p, 8 * 2 * E, hipMemcpyDeviceToHost, st));
+    if (vertexLoad && V) HIPCHK(hipMemcpyAsync(vertexLoad, d_vout.p, 8 * V, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipEventElapsedTime(&ms, R.ev.e[0], R.ev.e[1]));
+    ls->load_kernel_ms += ms;
+    ls->routed = (int64_t)cnt[LD_ROUTED];
+    ls->broken = (int64_t)cnt[LD_BROKEN];
+    ls->hop_weight = cnt[LD_HOPW];
+    ls->tree_vertices = (int64_t)cnt[LD_TREE];
+    return ls->routed;
+}
+
 }  // namespace
 
 extern "C" {
@@ -4381,6 +4547,46 @@ int shdtopo_trace_stats(Topology* top, ShdTraceStats* out) {
     if (!top || !out) return -1;
     std::lock_guard<std::mutex> lk(top->buildMu);
     *out = top->traceStats;
+    return 0;
+}
+
+int64_t shdtopo_link_load(Topology* top, const uint32_t* srcIP, const uint32_t* dstIP,
+                          const uint64_t* weight, int64_t n, uint64_t* edgeLoad,
+                          uint64_t* vertexLoad) {
+    if (!top || n < 0 || n > 0x7FFFFFFE) return -1;
+    if (n > 0 && (!srcIP || !dstIP)) return -1;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::lock_guard<std::mutex> lk(top->buildMu);
+    ShdLoadStats ls{};
+    ls.requests = n;
+    compute_geometry(top);
+    // the outputs are overwritten, not accumulated into
+    if (edgeLoad) std::fill(edgeLoad, edgeLoad + 2 * (size_t)top->g.E, (uint64_t)0);
+    if (vertexLoad) std::fill(vertexLoad, vertexLoad + (size_t)top->g.V, (uint64_t)0);
+    // both ends on a vertex of the current attached set, as a trace
+    std::vector<int32_t> sv((size_t)n), dv((size_t)n);
+    int64_t nvalid = 0;
+    for (int64_t i = 0; i < n; i++) {
+        int32_t s = vertex_of_ip(top, srcIP[i]), d = vertex_of_ip(top, dstIP[i]);
+        if (s >= 0 && (s >= top->g.V || top->colOf[(size_t)s] < 0)) s = -1;
+        if (d >= 0 && (d >= top->g.V || top->colOf[(size_t)d] < 0)) d = -1;
+        sv[(size_t)i] = s;
+        dv[(size_t)i] = d;
+        if (s >= 0 && d >= 0) nvalid++;
+    }
+    ls.unattached = n - nvalid;
+    int64_t routed = 0;
+    if (top->isComplete) routed = load_complete(top, sv, dv, weight, n, edgeLoad, vertexLoad, &ls);
+    else if (nvalid > 0) routed = load_replay(top, sv, dv, weight, n, edgeLoad, vertexLoad, &ls);
+    ls.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    top->loadStats = ls;
+    return routed;
+}
+
+int shdtopo_link_load_stats(Topology* top, ShdLoadStats* out) {
+    if (!top || !out) return -1;
+    std::lock_guard<std::mutex> lk(top->buildMu);
+    *out = top->loadStats;
     return 0;
 }
 

@@ -369,6 +369,45 @@ hipError_t launch_route_trace_scatter(const TraceReqs& rq, const TraceRoute* rou
                                       const int64_t* loff, const int32_t* stV, const int32_t* stE,
                                       int32_t* outV, int32_t* outE, hipStream_t stream);
 
+// ---- link load (topo_load.hip): per-edge and per-vertex traffic of a set of flows ----
+// Accumulators of one call and what the kernels need of the parsed graph.  eload u64[2E]: forward
+// half [0, E) (a hop leaves eu[e]; every self loop), reverse half [E, 2E); vload u64[V] in
+// relabelled ids (the weight arriving at each vertex).
+struct LoadAcc {
+    unsigned long long* eload = nullptr;
+    unsigned long long* vload = nullptr;
+    int64_t E = 0;
+    const int32_t* eu = nullptr;  // parsed edge tails (document order = edge id), original ids
+};
+// counters of one call (u64 words, zeroed by the caller)
+enum { LD_ROUTED = 0, LD_BROKEN, LD_HOPW, LD_TREE, LD_COUNT };
+// Validate: request q walks rdst -> rsrc with route_trace_kernel<1>'s guards; hops[q] = its hop
+// count (self pair: 1), -1 when broken; counts LD_ROUTED / LD_BROKEN and adds w x hops to LD_HOPW.
+hipError_t launch_load_validate(const ReplayCSR& g, const ReplayWs& ws, const TraceReqs& rq,
+                                const unsigned long long* w, int32_t* hops,
+                                unsigned long long* cnt, hipStream_t stream);
+// Per-request walk (option "load_walk"): two atomics per hop of every routed request.
+hipError_t launch_load_walk(const ReplayCSR& g, const ReplayWs& ws, const TraceIds& ids,
+                            const TraceReqs& rq, const unsigned long long* w,
+                            const int32_t* hops, const LoadAcc& acc, hipStream_t stream);
+// Tree accumulation.  The slots' vertex records are reused once the validation is over: the dist
+// words become the u64 weight of the vertex's subtree, the heap-position word {bit 31: visited,
+// bits 0..30: pending children}; reset clears both for the first nslots slots (the parent slot
+// word stays), claim marks the union of the requested chains and counts the children (hops[q]
+// becomes -2 for the request that marked its destination: the candidate starter), push carries
+// the weights leaf to root, one add per tree vertex into eload / vload.
+hipError_t launch_load_reset(const ReplayCSR& g, const ReplayWs& ws, int nslots,
+                             hipStream_t stream);
+hipError_t launch_load_claim(const ReplayCSR& g, const ReplayWs& ws, const TraceIds& ids,
+                             const TraceReqs& rq, const unsigned long long* w, int32_t* hops,
+                             const LoadAcc& acc, unsigned long long* cnt, hipStream_t stream);
+hipError_t launch_load_push(const ReplayCSR& g, const ReplayWs& ws, const TraceIds& ids,
+                            const TraceReqs& rq, const int32_t* hops, const LoadAcc& acc,
+                            hipStream_t stream);
+// out[perm[v]] = vload[v]: relabelled -> original vertex ids
+hipError_t launch_load_permute(int64_t V, const int32_t* perm, const unsigned long long* vload,
+                               unsigned long long* out, hipStream_t stream);
+
 hipError_t launch_pair_table_complete(int A, int64_t row0, int64_t rows, const double* elatAA,
                                       const double* elossAA, const double* vlossA, double2* out_lr,
                                       uint16_t* out_hops, double* out_rowmin,

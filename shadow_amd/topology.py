@@ -367,6 +367,39 @@ class Topology:
             raise RuntimeError("shdtopo_trace_stats failed")
         return {k: getattr(s, k) for k, _ in L.ShdTraceStats._fields_}
 
+    # ---- link load ----
+    def link_load(self, src_ips, dst_ips, weight=None):
+        """shdtopo_link_load: the weight the flows (src, dst, weight) put on every edge and
+        vertex along the routes trace_routes reports.  weight=None counts 1 per flow.  Returns a
+        dict of numpy uint64 arrays -- ``edge_fwd[e]`` (hops leaving eu[e]; self loops; every arc
+        of a directed topology), ``edge_rev[e]`` (hops leaving ev[e]), ``vertex[v]`` (the weight
+        arriving at v, original ids) -- and ``routed``, the flows that contributed."""
+        s = np.ascontiguousarray(src_ips, dtype=np.uint32)
+        d = np.ascontiguousarray(dst_ips, dtype=np.uint32)
+        if s.shape != d.shape or s.ndim != 1:
+            raise ValueError("src_ips and dst_ips must be 1-D and of one length")
+        n = len(s)
+        w = None
+        if weight is not None:
+            w = np.ascontiguousarray(weight, dtype=np.uint64)
+            if w.shape != s.shape:
+                raise ValueError("weight must have one entry per flow")
+        E, V = self.num_edges, self.num_vertices
+        edge = np.zeros(max(2 * E, 1), np.uint64)
+        vert = np.zeros(max(V, 1), np.uint64)
+        r = int(self._lib.shdtopo_link_load(self._h, _p(s), _p(d), _p(w) if w is not None else None,
+                                            n, _p(edge), _p(vert)))
+        if r < 0:
+            raise RuntimeError("shdtopo_link_load failed: %d" % r)
+        return {"edge_fwd": edge[:E], "edge_rev": edge[E:2 * E], "vertex": vert[:V], "routed": r}
+
+    def link_load_stats(self):
+        """The last link_load's own counters (shdtopo_link_load_stats)."""
+        s = L.ShdLoadStats()
+        if self._lib.shdtopo_link_load_stats(self._h, ctypes.byref(s)) != 0:
+            raise RuntimeError("shdtopo_link_load_stats failed")
+        return {k: getattr(s, k) for k, _ in L.ShdLoadStats._fields_}
+
     def write_graphml(self, path):
         if self._lib.shdtopo_write_graphml(self._h, path.encode()) != 0:
             raise RuntimeError("write_graphml failed")
