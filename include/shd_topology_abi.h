@@ -138,7 +138,11 @@ Topology* shdtopo_new_from_buffer(const char* graphml, size_t len);
  * shdtopo_link_load's launches too), "load_walk" (shdtopo_link_load: 1, the default, walks every
  * request's route with two atomics per hop; 0 sums the weights leaf to root over each source's
  * tree of requested routes, one add per tree vertex -- measured no faster at the bench size,
- * DESIGN.md 3.7; both give the same sums; any other value is rejected).
+ * DESIGN.md 3.7; both give the same sums; any other value is rejected), "trace_batch"
+ * (shdtopo_trace_routes / shdtopo_link_load: 1, the default, takes a source's routes from the
+ * batch kernel's parent records where that is exact and replays only the other sources; 0 always
+ * runs the heap replay -- the A/B and test baseline; both give the same bytes; any other value is
+ * rejected).
  * Returns 0 or -1 for an unknown key / bad value. */
 int shdtopo_set_option(Topology* top, const char* key, double value);
 
@@ -452,9 +456,16 @@ typedef struct {
  * In lazy mode on an undirected topology topology_getLatency(a, b) may be answered from row b
  * (first-rooted-wins, shd-topology.c:896-915) and then equals trace(b, a), not trace(a, b).
  *
- * SSSP topologies: the distinct sources run through the exact heap replay (seconds per source
- * at a million vertices), in chunks of at most its wavefront slots (option
- * "trace_chunk"); the first trace uploads the edge ids (4 B per adjacency entry).  Complete
+ * SSSP topologies: the distinct sources are taken in chunks (option "trace_chunk"; at most the
+ * replay's wavefront slots and the batch kernel's slots x sources per batch).  A chunk runs the
+ * batch kernel once on its sources (option "trace_batch" = 1, the default; milliseconds per
+ * source) and walks the parent records that launch leaves; a source whose row crosses a tied
+ * parent -- the rows a table build hands to the heap replay -- or has a broken requested chain
+ * runs through the exact heap replay instead (seconds per source at a million vertices,
+ * DESIGN.md 3.6), and so does every source when the batch kernel does not apply: a tie-dense
+ * topology, a multigraph, "replay_all", a target set the relaxation copy was not prepared for
+ * (hosts attached since the last build), or "trace_batch" = 0.  Both paths give the same bytes.
+ * The first trace uploads the edge ids (4 B per adjacency entry).  Complete
  * topologies (_topology_lookupPath, :835-873: one hop over the direct edge) are answered on the
  * host from the parsed graph: no device, no table.  A multi-device topology traces on its first
  * device.  A trace materialises no lazy row, pushes no minimum, neither invalidates nor rebuilds
@@ -471,13 +482,16 @@ int64_t shdtopo_format_route(Topology* top, const ShdRoute* r, const int32_t* ve
 /* the last trace's own counters (ShdStats is not touched by a trace) */
 typedef struct {
     double total_ms;        /* wall time of the call */
-    double replay_ms;       /* event time of its heap-replay launches */
+    double replay_ms;       /* event time of its heap-replay launches only */
     double trace_kernel_ms; /* event time of route_trace_kernel, its scans, placement and scatter */
     double ids_ms;          /* wall time of the edge-id upload (first trace of a topology, else 0) */
     int64_t requests;       /* n */
-    int64_t sources;        /* distinct source vertices replayed */
-    int64_t chunks;         /* replay launches */
+    int64_t sources;        /* distinct source vertices of the call, either path */
+    int64_t chunks;         /* source chunks */
     int64_t entries;        /* the call's return value */
+    double batch_ms;        /* event time of the batch kernel's keep launches */
+    int64_t batch_sources;  /* distinct sources answered from the batch kernel's parent records */
+    int64_t batch_fallback; /* sources that ran a keep launch and then went to the heap replay */
 } ShdTraceStats;
 int shdtopo_trace_stats(Topology* top, ShdTraceStats* out);
 
@@ -503,27 +517,33 @@ int shdtopo_trace_stats(Topology* top, ShdTraceStats* out);
  * that contributed, or a negative error (-1: bad arguments -- NULL top, n < 0, a NULL IP array
  * with n > 0).
  *
- * SSSP topologies: the distinct sources run through the exact heap replay in chunks (option
- * "trace_chunk"), as a trace; the accumulation itself is microseconds to milliseconds next to it
- * (option "load_walk" selects between the per-request walk and the tree sums).  Complete topologies are
+ * SSSP topologies: the distinct sources are taken in chunks (option "trace_chunk") and get their
+ * chains as in a trace: from the batch kernel's parent records where that is exact (option
+ * "trace_batch"), else from the exact heap replay.  The accumulation itself is microseconds to
+ * milliseconds (option "load_walk" selects between the per-request walk and the
+ * tree sums; the tree sums keep their state in the replay's records, so "load_walk" = 0 replays
+ * every source).  Complete topologies are
  * answered on the host from the parsed graph: no device is used.  A multi-device topology runs on
  * its first device.  Like a trace, the call materialises no lazy row, pushes no minimum, neither
  * invalidates nor rebuilds the table and leaves ShdStats as it was. */
 typedef struct {
     double  total_ms;        /* wall time of the call */
-    double  replay_ms;       /* event time of its heap-replay launches */
+    double  replay_ms;       /* event time of its heap-replay launches only */
     double  load_kernel_ms;  /* event time of the accumulation kernels (everything but the replay) */
     double  ids_ms;          /* edge-id upload, first trace/load of a topology, else 0 */
     int64_t requests;        /* n */
     int64_t routed;          /* requests that contributed */
     int64_t unattached;      /* requests with an unattached end (contribute nothing) */
     int64_t broken;          /* unroutable / broken chain / self pair without a self loop */
-    int64_t sources;         /* distinct source vertices replayed */
-    int64_t chunks;          /* replay launches */
+    int64_t sources;         /* distinct source vertices of the call, either path */
+    int64_t chunks;          /* source chunks */
     int64_t tree_vertices;   /* sum over sources of the vertices in the union of its requested chains
                                 (the source aside: = adds into the edge accumulators, self pairs
                                 apart); 0 for the per-request walk */
     uint64_t hop_weight;     /* sum over routed requests of weight x hops (= sum of edgeLoad) */
+    double  batch_ms;        /* event time of the batch kernel's keep launches */
+    int64_t batch_sources;   /* distinct sources answered from the batch kernel's parent records */
+    int64_t batch_fallback;  /* sources that ran a keep launch and then went to the heap replay */
 } ShdLoadStats;
 
 int64_t shdtopo_link_load(Topology* top, const uint32_t* srcIP, const uint32_t* dstIP,

@@ -71,13 +71,15 @@ class ShdRoute(ctypes.Structure):
 
 class ShdTraceStats(ctypes.Structure):
     _fields_ = [("total_ms", dbl), ("replay_ms", dbl), ("trace_kernel_ms", dbl), ("ids_ms", dbl),
-                ("requests", i64), ("sources", i64), ("chunks", i64), ("entries", i64)]
+                ("requests", i64), ("sources", i64), ("chunks", i64), ("entries", i64),
+                ("batch_ms", dbl), ("batch_sources", i64), ("batch_fallback", i64)]
 
 
 class ShdLoadStats(ctypes.Structure):
     _fields_ = [("total_ms", dbl), ("replay_ms", dbl), ("load_kernel_ms", dbl), ("ids_ms", dbl),
                 ("requests", i64), ("routed", i64), ("unattached", i64), ("broken", i64),
-                ("sources", i64), ("chunks", i64), ("tree_vertices", i64), ("hop_weight", u64)]
+                ("sources", i64), ("chunks", i64), ("tree_vertices", i64), ("hop_weight", u64),
+                ("batch_ms", dbl), ("batch_sources", i64), ("batch_fallback", i64)]
 
 
 class ShdSynthParams(ctypes.Structure):

@@ -450,6 +450,8 @@ struct _Topology {
     // uploaded by the first trace -- relabelled -> original vertex, the igraph_get_eid edge of
     // every replay-CSR entry, the lowest-id self loop of every vertex
     int traceChunk = 0;       // option "trace_chunk": sources per replay launch (0 = the slots)
+    int traceBatch = 1;       // option "trace_batch": 1 = chains from the batch kernel's pair
+                              // records where eligible (prepare_batch_path), 0 = always replay
     bool traceIdsReady = false;
     DevBuf<int32_t> d_tperm, d_reid, d_selfEid;
     ShdTraceStats traceStats{};  // the last trace's own counters
@@ -1417,6 +1419,26 @@ double default_delta(Topology* top) {
     return std::max(1e-9, 1.0 * mean);
 }
 
+// bucket shifts of the sources s[0 .. n) (relabelled ids): sh = C - d(src, h0) >= 2 delta puts
+// every source's h0 at C (h0_shift; topo_sssp_batch.hip)
+std::vector<double> source_shifts(Topology* top, const uint32_t* s, int64_t n, double delta) {
+    const double pmax = top->hp->to_h0_max();  // largest finite d(., h0) (upload_csr)
+    const double C = h0_shift(top, delta);
+    std::vector<double> sh((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        const double p = top->hp->to_h0(s[(size_t)i]);
+        sh[(size_t)i] = C - (std::isfinite(p) ? p : pmax);
+    }
+    return sh;
+}
+
+// LDS plan of a batched launch under the current options (lds_hubs, par_hubs)
+SsspLdsPlan batch_lds_plan(Topology* top, int K) {
+    return sssp_batch_lds_plan(
+        K, top->hubLimit, (uint32_t)std::max<int64_t>(0, std::min<int64_t>(top->parHubs, 1 << 20)),
+        top->g.V);
+}
+
 // The batch layout of a launch goes to the device: output row (rowmap) and source of each
 // position, its bucket shift sh = C - d(src, h0) >= 2 delta (every source's h0 at C, h0_shift;
 // topo_sssp_batch.hip), and the batch starts of a measured layout.
@@ -1430,13 +1452,7 @@ int upload_layout(Topology* top, const std::vector<uint32_t>& src, const std::ve
     HIPCHK(top->d_bsrc.ensure((size_t)rows));
     HIPCHK(hipMemcpyAsync(top->d_rowmap.p, perm.data(), 4 * (size_t)rows, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(top->d_bsrc.p, psrc.data(), 4 * (size_t)rows, hipMemcpyHostToDevice, st));
-    const double pmax = top->hp->to_h0_max();  // largest finite d(., h0) (upload_csr)
-    const double C = h0_shift(top, delta);
-    std::vector<double> sh((size_t)rows);
-    for (int64_t i = 0; i < rows; i++) {
-        const double p = top->hp->to_h0(psrc[(size_t)i]);
-        sh[(size_t)i] = C - (std::isfinite(p) ? p : pmax);
-    }
+    const std::vector<double> sh = source_shifts(top, psrc.data(), rows, delta);
     HIPCHK(top->d_srcsh.ensure((size_t)rows));
     HIPCHK(hipMemcpyAsync(top->d_srcsh.p, sh.data(), sizeof(double) * (size_t)rows,
                           hipMemcpyHostToDevice, st));
@@ -1833,22 +1849,14 @@ int enqueue_rows(Topology* top, int64_t row0, int64_t row1, double2* out_lr, uin
                     const auto tq0 = std::chrono::steady_clock::now();
                     const int64_t P = kTieProbeRows;
                     const double delta = default_delta(top);
-                    const double pmax = top->hp->to_h0_max();
-                    const double C = h0_shift(top, delta);
-                    std::vector<double> sh((size_t)P);
-                    for (int64_t i = 0; i < P; i++) {
-                        const double pp = top->hp->to_h0(src[(size_t)i]);
-                        sh[(size_t)i] = C - (std::isfinite(pp) ? pp : pmax);
-                    }
+                    const std::vector<double> sh = source_shifts(top, src.data(), P, delta);
                     HIPCHK(top->d_probeSrc.ensure((size_t)P));
                     HIPCHK(top->d_probeSh.ensure((size_t)P));
                     HIPCHK(hipMemcpyAsync(top->d_probeSrc.p, src.data(), 4 * (size_t)P, hipMemcpyHostToDevice, st));
                     HIPCHK(hipMemcpyAsync(top->d_probeSh.p, sh.data(), 8 * (size_t)P, hipMemcpyHostToDevice, st));
                     SlotWs pws = ws;
                     pws.rowmap = nullptr;  // sample row i -> output row i
-                    const SsspLdsPlan bp = sssp_batch_lds_plan(
-                        K, top->hubLimit, (uint32_t)std::max<int64_t>(0, std::min<int64_t>(top->parHubs, 1 << 20)),
-                        top->g.V);
+                    const SsspLdsPlan bp = batch_lds_plan(top, K);
                     r = hub_rows_ready(top, bp.H, st);
                     if (r) return r;
                     HIPCHK(launch_sssp_batch(K, dev_csr(top), pws, top->d_probeSrc.p, top->d_probeSh.p,
@@ -2037,9 +2045,7 @@ int enqueue_rows(Topology* top, int64_t row0, int64_t row1, double2* out_lr, uin
                 top->stats.order_ms = std::chrono::duration<double, std::milli>(
                     std::chrono::steady_clock::now() - to0).count();
                 HIPCHK(hipEventRecord(top->ev0, st));
-                const SsspLdsPlan bp = sssp_batch_lds_plan(
-                    K, top->hubLimit, (uint32_t)std::max<int64_t>(0, std::min<int64_t>(top->parHubs, 1 << 20)),
-                    top->g.V);
+                const SsspLdsPlan bp = batch_lds_plan(top, K);
                 top->stats.lds_hubs = bp.H;
                 r = hub_rows_ready(top, bp.H, st);
                 if (r) return r;
@@ -3391,6 +3397,10 @@ int shdtopo_set_option(Topology* top, const char* key, double value) {
         if (value != 0 && value != 1) return -1;
         top->loadWalk = (int)value;
     }
+    else if (k == "trace_batch") {
+        if (value != 0 && value != 1) return -1;
+        top->traceBatch = (int)value;
+    }
     else if (k == "tie_dense") top->tieDenseOpt = value < 0 ? -1 : (value != 0 ? 1 : 0);
     else if (k == "source_order") top->sourceOrder = (int)value;
     else if (k == "batch_order") top->batchOrder = (int)value;
@@ -4190,7 +4200,9 @@ struct TraceKeep {
     }
 };
 struct TraceEvents {
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+    // 0 / 1 bracket a chunk's replay launch, 2 closes the chunk; 3 / 4 bracket its keep launch,
+    // 5 / 6 the pair walks' first pass
+    hipEvent_t e[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     ~TraceEvents() {
         for (hipEvent_t x : e)
             if (x) (void)hipEventDestroy(x);
@@ -4212,6 +4224,25 @@ struct ReplayReqs {
     DevBuf<uint32_t> d_srcs, d_rslot, d_rsrc, d_rdst, d_ridx;
     DevBuf<unsigned long long> d_st;  // its own counters: the last build's stay intact
     TraceEvents ev;
+    // The batch path (option "trace_batch", prepare_batch_path): a chunk's sources first run the
+    // batch kernel's keep launch, kf per batch and slot; the sources whose row it leaves
+    // unflagged are walked from the slots' pair records, the others replayed.  Everything the
+    // launch writes besides the batch workspace is the call's: targets, shifts, row flags, stats.
+    bool batchOk = false;
+    int K = 0, kf = 0;
+    double delta = 0.0;
+    SsspLdsPlan plan;
+    DevCSR bcsr;
+    SlotWs bws;
+    PairChains pc;
+    DevBuf<uint32_t> d_tgt, d_rmap, d_fsrcs;
+    DevBuf<double> d_srcsh;
+    DevBuf<uint8_t> d_rowflag, d_broken;
+    DevBuf<unsigned long long> d_bst;
+    // one chunk's chains (chunk_chains): rmap[i] of chunk source i, the sources replayed
+    std::vector<uint32_t> rmap;
+    bool mixed = false;  // the chunk ran a keep launch: its requests carry rmap
+    int nfall = 0;       // sources of the chunk that were replayed
     TraceReqs reqs(int s0, int s1) const {
         TraceReqs rq;
         const size_t q0 = srcStart[(size_t)s0];
@@ -4224,11 +4255,64 @@ struct ReplayReqs {
     }
 };
 
+// Whether this call's chains may come from the batch kernel, and if so what its
+// keep launches need.  The launch must compute the rows a table build of the current attached set
+// would: the build's conditions for running the batch kernel at all (the allReplay rule of
+// enqueue_rows), its workspace, and a relaxation copy that is usable for the current target set
+// as it stands -- a trace neither prepares a target set nor restores the plain copy.  The tree
+// accumulation of a link load keeps its state in the replay's records (forLoadTree): replay.
+int prepare_batch_path(Topology* top, const std::vector<uint32_t>& tgt, bool forLoadTree,
+                       ReplayReqs& R) {
+    R.batchOk = false;
+    if (!top->traceBatch || top->isComplete || forLoadTree) return 0;
+    const bool dense = top->tieReplay && (top->tieDenseOpt == 1 ||
+                                          (top->tieDenseOpt < 0 && top->tieDense));
+    if (top->replayAll || top->hasMultiEdges || dense) return 0;
+    const bool copyOk = top->adjkPlain ? !top->targetSkip : top->adjkTargets == tgt;
+    if (!copyOk || !top->d_adjk.p || !top->d_adj.p) return 0;
+    const int K = batch_k(top);
+    const size_t hparN = (size_t)std::min<int64_t>(top->parHubs, 1 << 20) * K;
+    if (top->slots <= 0 || top->wsK != K || top->wsRing != ring_entries(top, K) ||
+        top->wsHpar < hparN || top->wsRsChunk != top->rsChunk) {
+        // no workspace of this layout (released, or never built here): the next build's
+        if (ensure_workspace(top, R.nsrc) != 0) {
+            (void)hipGetLastError();
+            return 0;
+        }
+        // the one thing of this call that ShdStats keeps: the workspace a later build will find
+        R.keep->stats.slots = top->stats.slots;
+        R.keep->stats.workspace_bytes = top->stats.workspace_bytes;
+        R.keep->stats.workspace_ms = top->stats.workspace_ms;
+    }
+    if (top->slots <= 0) return 0;
+    R.K = K;
+    const int fill = (int)top->stats.batch_fill;  // consecutive groups of the build's fill
+    R.kf = fill >= 1 && fill <= K ? fill : K;
+    R.delta = default_delta(top);
+    R.plan = batch_lds_plan(top, K);
+    R.bcsr = dev_csr(top);
+    R.bws = slot_ws(top);
+    R.pc.prec = R.bws.prec;
+    R.pc.counters = R.bws.counters;
+    R.pc.slots = R.bws.slots;
+    R.pc.K = K;
+    R.pc.kf = R.kf;
+    const int64_t A = (int64_t)tgt.size();
+    const std::vector<double> sh = source_shifts(top, R.srcs.data(), R.nsrc, R.delta);
+    HIPCHK(R.d_tgt.ensure((size_t)std::max<int64_t>(1, A)));
+    HIPCHK(R.d_srcsh.ensure((size_t)R.nsrc));
+    HIPCHK(R.d_bst.ensure(ST_COUNT));
+    HIPCHK(hipMemcpy(R.d_tgt.p, tgt.data(), 4 * (size_t)A, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(R.d_srcsh.p, sh.data(), 8 * (size_t)R.nsrc, hipMemcpyHostToDevice));
+    R.batchOk = true;
+    return 0;
+}
+
 // sv / dv: the requests' vertices (-1 = not attached).  Prepares the device, the replay and the
-// edge ids (*ids_ms), and fills R.
+// edge ids (*ids_ms), and fills R.  forLoadTree: a link load with the tree accumulation.
 int group_replay_requests(Topology* top, const std::vector<int32_t>& sv,
                           const std::vector<int32_t>& dv, int64_t n, double* ids_ms,
-                          ReplayReqs& R) {
+                          bool forLoadTree, ReplayReqs& R) {
     int r = dev_init(top);
     if (r) return r;
     r = collect_row_stats(top);  // the last build's counters are read before the replay is reused
@@ -4276,7 +4360,12 @@ int group_replay_requests(Topology* top, const std::vector<int32_t>& sv,
     if (r) return r;
     R.csr = replay_csr(top);
     R.ws = replay_ws(top);
+    r = prepare_batch_path(top, tgt, forLoadTree, R);
+    if (r) return r;
+    // a chunk's sources fit the replay's slots and, on the batch path, one batch per batch slot
     int chunk = R.ws.slots;
+    if (R.batchOk)
+        chunk = (int)std::min<int64_t>(chunk, (int64_t)R.bws.slots * R.kf);
     if (top->traceChunk > 0) chunk = std::min(chunk, top->traceChunk);
     if (chunk < 1) return -3;
     R.chunk = chunk;
@@ -4289,6 +4378,12 @@ int group_replay_requests(Topology* top, const std::vector<int32_t>& sv,
     HIPCHK(R.d_rslot.ensure(nv)); HIPCHK(R.d_rsrc.ensure(nv)); HIPCHK(R.d_rdst.ensure(nv));
     HIPCHK(R.d_ridx.ensure(nv));
     HIPCHK(R.d_st.ensure(ST_COUNT));
+    if (R.batchOk) {
+        HIPCHK(R.d_rmap.ensure((size_t)chunk));
+        HIPCHK(R.d_fsrcs.ensure((size_t)chunk));
+        HIPCHK(R.d_rowflag.ensure((size_t)chunk));
+        HIPCHK(R.d_broken.ensure((size_t)chunk));
+    }
     HIPCHK(hipMemcpy(R.d_srcs.p, srcs.data(), 4 * (size_t)nsrc, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(R.d_rslot.p, rslot.data(), 4 * nv, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(R.d_rsrc.p, rsrc.data(), 4 * nv, hipMemcpyHostToDevice));
@@ -4310,12 +4405,118 @@ int launch_replay_chunk(Topology* top, ReplayReqs& R, int s0, int s1) {
     return 0;
 }
 
-// SSSP topologies: replay the distinct sources in chunks, walk the requests' chains (topo_trace.hip)
+// The chains of chunk [s0, s1) of R's sources, *rq its requests.  Without the batch path: the
+// replay of every source, as launch_replay_chunk.  With it:
+//   keep launch of the chunk's sources (ev 3 / 4), its row flags and ST_ERRORS read back;
+//   rmap: an unflagged source is served from its batch slot's pair records, a flagged one -- the
+//     rows a table build replays -- gets a replay slot;
+//   pairs1(rq, again): the caller's first pass over the pair records (the trace's count, the
+//     load's validation; ev 5 / 6), which marks the sources with a broken requested chain in
+//     R.d_broken.  Only a launch that counted errors can have one: then the marks are read, those
+//     sources join the replay list and pairs1 runs once more (again = true) without them;
+//   the replay of the listed sources in slots 0 .. nfall - 1 (ev 0 / 1).
+// On return rq carries rmap, R.nfall says how many sources were replayed (their first pass is
+// the caller's), and the times and counts are added to the three statistics.
+template <class F>
+int chunk_chains(Topology* top, ReplayReqs& R, int s0, int s1, TraceReqs* rq, F&& pairs1,
+                 double* batch_ms, int64_t* batch_sources, int64_t* batch_fallback) {
+    hipStream_t st = top->stream;
+    R.mixed = false;
+    if (!R.batchOk) {
+        R.nfall = s1 - s0;
+        return launch_replay_chunk(top, R, s0, s1);
+    }
+    const int ns = s1 - s0;
+    R.mixed = true;
+    HIPCHK(hipMemsetAsync(R.d_bst.p, 0, sizeof(unsigned long long) * ST_COUNT, st));
+    HIPCHK(hipMemsetAsync(R.d_rowflag.p, 0, (size_t)ns, st));
+    HIPCHK(hipMemsetAsync(R.d_broken.p, 0, (size_t)ns, st));
+    int r = hub_rows_ready(top, R.plan.H, st);
+    if (r) return r;
+    SlotWs ws = R.bws;
+    ws.rowflag = R.d_rowflag.p;
+    HIPCHK(hipEventRecord(R.ev.e[3], st));
+    HIPCHK(launch_sssp_batch_keep(R.K, R.bcsr, ws, R.d_srcs.p + s0, R.d_srcsh.p + s0, ns, R.kf,
+                                  R.d_tgt.p, (int)top->A, R.delta, R.plan, top->iterGuard,
+                                  R.d_bst.p, st));
+    HIPCHK(hipEventRecord(R.ev.e[4], st));
+    std::vector<uint8_t> fl((size_t)ns), br((size_t)ns, 0);
+    unsigned long long bst[ST_OVERFLOW + 1] = {};
+    HIPCHK(hipMemcpyAsync(fl.data(), R.d_rowflag.p, (size_t)ns, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(bst, R.d_bst.p, sizeof bst, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, R.ev.e[3], R.ev.e[4]));
+    *batch_ms += ms;
+    // a launch that overflowed a queue or tripped the iteration guard is not trusted: replay
+    const bool distrust = bst[ST_OVERFLOW] != 0;
+    std::vector<uint32_t> fsrc;
+    auto build_map = [&]() {
+        R.rmap.assign((size_t)ns, kNoReplaySlot);
+        fsrc.clear();
+        for (int i = 0; i < ns; i++)
+            if (distrust || fl[(size_t)i] || br[(size_t)i]) {
+                R.rmap[(size_t)i] = (uint32_t)fsrc.size();
+                fsrc.push_back(R.srcs[(size_t)(s0 + i)]);
+            }
+        return hipMemcpy(R.d_rmap.p, R.rmap.data(), 4 * (size_t)ns, hipMemcpyHostToDevice);
+    };
+    HIPCHK(build_map());
+    rq->rmap = R.d_rmap.p;
+    rq->nmap = (uint32_t)ns;
+    if ((int)fsrc.size() < ns) {
+        HIPCHK(hipEventRecord(R.ev.e[5], st));
+        r = pairs1(*rq, false);
+        if (r) return r;
+        if (bst[ST_ERRORS]) {
+            HIPCHK(hipMemcpyAsync(br.data(), R.d_broken.p, (size_t)ns, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            bool any = false;
+            for (int i = 0; i < ns; i++) any |= br[(size_t)i] != 0 && R.rmap[(size_t)i] == kNoReplaySlot;
+            if (any) {
+                HIPCHK(build_map());
+                r = pairs1(*rq, true);
+                if (r) return r;
+            }
+        }
+        HIPCHK(hipEventRecord(R.ev.e[6], st));
+    }
+    R.nfall = (int)fsrc.size();
+    *batch_sources += ns - R.nfall;
+    *batch_fallback += R.nfall;
+    HIPCHK(hipMemsetAsync(R.d_st.p, 0, sizeof(unsigned long long) * ST_COUNT, st));
+    HIPCHK(hipEventRecord(R.ev.e[0], st));
+    if (R.nfall > 0) {
+        HIPCHK(hipMemcpy(R.d_fsrcs.p, fsrc.data(), 4 * fsrc.size(), hipMemcpyHostToDevice));
+        HIPCHK(launch_heap_replay_trace(R.csr, R.ws, R.d_fsrcs.p, R.nfall, R.d_st.p, st));
+    }
+    HIPCHK(hipEventRecord(R.ev.e[1], st));
+    return 0;
+}
+// event times of a chunk after its closing event (ev 2) and a stream sync: the replay launch (if
+// one ran) and everything else but the keep launch
+int chunk_times(ReplayReqs& R, double* replay_ms, double* kernel_ms) {
+    float ms = 0;
+    if (R.nfall > 0) {
+        HIPCHK(hipEventElapsedTime(&ms, R.ev.e[0], R.ev.e[1]));
+        *replay_ms += ms;
+    }
+    HIPCHK(hipEventElapsedTime(&ms, R.ev.e[1], R.ev.e[2]));
+    *kernel_ms += ms;
+    if (R.mixed && R.nfall < (int)R.rmap.size()) {
+        HIPCHK(hipEventElapsedTime(&ms, R.ev.e[5], R.ev.e[6]));
+        *kernel_ms += ms;
+    }
+    return 0;
+}
+
+// SSSP topologies: the distinct sources in chunks -- chains from the batch kernel's pair records
+// or the replay (chunk_chains) -- and the walks of the requests' chains (topo_trace.hip)
 int64_t trace_replay(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
                      int64_t n, ShdRoute* routes, int32_t* vertices, int32_t* edges, int64_t cap,
                      ShdTraceStats* ts) {
     ReplayReqs R;
-    int r = group_replay_requests(top, sv, dv, n, &ts->ids_ms, R);
+    int r = group_replay_requests(top, sv, dv, n, &ts->ids_ms, false, R);
     if (r) return r;
     hipStream_t st = top->stream;
     const std::vector<uint32_t>& srcStart = R.srcStart;
@@ -4343,12 +4544,20 @@ int64_t trace_replay(Topology* top, const std::vector<int32_t>& sv, const std::v
     float ms = 0;
     for (int s0 = 0; s0 < nsrc; s0 += chunk) {
         const int s1 = std::min(nsrc, s0 + chunk);
-        const TraceReqs rq = reqs(s0, s1);
+        TraceReqs rq = reqs(s0, s1);
         const size_t q0 = srcStart[(size_t)s0], m = (size_t)rq.n;
-        r = launch_replay_chunk(top, R, s0, s1);
-        if (r) return r;
         HIPCHK(hipMemsetAsync(d_lneed.p, 0, 8 * (m + 1), st));
-        HIPCHK(launch_route_trace_count(csr, ws, rq, d_routes.p, d_lneed.p, d_gneed.p, st));
+        // both chain sources write the same routes, needs and staging: each takes its requests
+        r = chunk_chains(top, R, s0, s1, &rq,
+                         [&](const TraceReqs& q, bool) {
+                             HIPCHK(launch_route_trace_count_pairs(csr, R.pc, q, d_routes.p, d_lneed.p,
+                                                                   d_gneed.p, R.d_broken.p, st));
+                             return 0;
+                         },
+                         &ts->batch_ms, &ts->batch_sources, &ts->batch_fallback);
+        if (r) return r;
+        if (R.nfall > 0)
+            HIPCHK(launch_route_trace_count(csr, ws, rq, d_routes.p, d_lneed.p, d_gneed.p, st));
         HIPCHK(trace_exclusive_scan(d_lneed.p, d_coff.p, (int64_t)m + 1, st));
         int64_t tot = 0;
         HIPCHK(hipMemcpy(&tot, d_coff.p + m, 8, hipMemcpyDeviceToHost));
@@ -4358,14 +4567,16 @@ int64_t trace_replay(Topology* top, const std::vector<int32_t>& sv, const std::v
         DevBuf<int32_t>& stE = *stage[stage.size() - 1];
         HIPCHK(stV.ensure((size_t)std::max<int64_t>(1, tot)));
         HIPCHK(stE.ensure((size_t)std::max<int64_t>(1, tot)));
-        HIPCHK(launch_route_trace_write(csr, ws, ids, rq, d_routes.p, d_coff.p, stV.p, stE.p, st));
+        if (R.mixed && R.nfall < s1 - s0)
+            HIPCHK(launch_route_trace_write_pairs(csr, R.pc, ids, rq, d_routes.p, d_coff.p, stV.p,
+                                                  stE.p, st));
+        if (R.nfall > 0)
+            HIPCHK(launch_route_trace_write(csr, ws, ids, rq, d_routes.p, d_coff.p, stV.p, stE.p, st));
         HIPCHK(hipMemcpyAsync(d_loff.p + q0, d_coff.p, 8 * m, hipMemcpyDeviceToDevice, st));
         HIPCHK(hipEventRecord(ev.e[2], st));
         HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-        ts->replay_ms += ms;
-        HIPCHK(hipEventElapsedTime(&ms, ev.e[1], ev.e[2]));
-        ts->trace_kernel_ms += ms;
+        r = chunk_times(R, &ts->replay_ms, &ts->trace_kernel_ms);
+        if (r) return r;
         ts->chunks++;
     }
 
@@ -4429,12 +4640,13 @@ int64_t load_complete(Topology* top, const std::vector<int32_t>& sv, const std::
     return ls->routed;
 }
 
-// SSSP topologies: replay the distinct sources in chunks and accumulate along the chains
+// SSSP topologies: the distinct sources in chunks -- chains from the batch kernel's pair records
+// (the per-request walk only) or the replay (chunk_chains) -- and the sums along the chains
 int64_t load_replay(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
                     const uint64_t* weight, int64_t n, uint64_t* edgeLoad, uint64_t* vertexLoad,
                     ShdLoadStats* ls) {
     ReplayReqs R;
-    int r = group_replay_requests(top, sv, dv, n, &ls->ids_ms, R);
+    int r = group_replay_requests(top, sv, dv, n, &ls->ids_ms, !top->loadWalk, R);
     if (r) return r;
     hipStream_t st = top->stream;
     const size_t nv = R.nv, V = (size_t)top->g.V, E = (size_t)top->g.E;
@@ -4443,7 +4655,7 @@ int64_t load_replay(Topology* top, const std::vector<int32_t>& sv, const std::ve
     std::vector<unsigned long long> rw(nv, 1ull);
     if (weight)
         for (size_t q = 0; q < nv; q++) rw[q] = weight[R.order[q]];
-    DevBuf<unsigned long long> d_w, d_eload, d_vload, d_vout, d_cnt;
+    DevBuf<unsigned long long> d_w, d_eload, d_vload, d_vout, d_cnt, d_pcnt;
     DevBuf<int32_t> d_hops;
     HIPCHK(d_w.ensure(nv));
     HIPCHK(d_hops.ensure(nv));
@@ -4451,6 +4663,7 @@ int64_t load_replay(Topology* top, const std::vector<int32_t>& sv, const std::ve
     HIPCHK(d_vload.ensure(V));
     HIPCHK(d_vout.ensure(V));
     HIPCHK(d_cnt.ensure(LD_COUNT));
+    HIPCHK(d_pcnt.ensure(LD_COUNT));
     HIPCHK(hipMemcpy(d_w.p, rw.data(), 8 * nv, hipMemcpyHostToDevice));
     HIPCHK(hipMemsetAsync(d_eload.p, 0, 8 * std::max<size_t>(1, 2 * E), st));
     HIPCHK(hipMemsetAsync(d_vload.p, 0, 8 * std::max<size_t>(1, V), st));
@@ -4463,16 +4676,34 @@ int64_t load_replay(Topology* top, const std::vector<int32_t>& sv, const std::ve
     acc.eu = top->d_eu.p;
 
     float ms = 0;
+    // counters of the pair walks' validation: per chunk in d_pcnt (a validation that finds a
+    // broken chain is run again without that source), summed here
+    unsigned long long pcnt[LD_COUNT] = {};
     for (int s0 = 0; s0 < R.nsrc; s0 += R.chunk) {
         const int s1 = std::min(R.nsrc, s0 + R.chunk);
-        const TraceReqs rq = R.reqs(s0, s1);
+        TraceReqs rq = R.reqs(s0, s1);
         const size_t q0 = R.srcStart[(size_t)s0];
-        r = launch_replay_chunk(top, R, s0, s1);
+        r = chunk_chains(top, R, s0, s1, &rq,
+                         [&](const TraceReqs& q, bool) {
+                             HIPCHK(hipMemsetAsync(d_pcnt.p, 0, 8 * LD_COUNT, st));
+                             HIPCHK(launch_load_validate_pairs(R.csr, R.pc, q, d_w.p + q0,
+                                                               d_hops.p + q0, d_pcnt.p,
+                                                               R.d_broken.p, st));
+                             return 0;
+                         },
+                         &ls->batch_ms, &ls->batch_sources, &ls->batch_fallback);
         if (r) return r;
-        HIPCHK(launch_load_validate(R.csr, R.ws, rq, d_w.p + q0, d_hops.p + q0, d_cnt.p, st));
-        if (top->loadWalk) {
+        const bool pairs = R.mixed && R.nfall < s1 - s0;
+        unsigned long long c[LD_COUNT] = {};
+        if (pairs) {
+            HIPCHK(hipMemcpyAsync(c, d_pcnt.p, 8 * LD_COUNT, hipMemcpyDeviceToHost, st));
+            HIPCHK(launch_load_walk_pairs(R.csr, R.pc, R.ids, rq, d_w.p + q0, d_hops.p + q0, acc, st));
+        }
+        if (R.nfall > 0)
+            HIPCHK(launch_load_validate(R.csr, R.ws, rq, d_w.p + q0, d_hops.p + q0, d_cnt.p, st));
+        if (R.nfall > 0 && top->loadWalk) {
             HIPCHK(launch_load_walk(R.csr, R.ws, R.ids, rq, d_w.p + q0, d_hops.p + q0, acc, st));
-        } else {
+        } else if (R.nfall > 0) {
             HIPCHK(launch_load_reset(R.csr, R.ws, s1 - s0, st));
             HIPCHK(launch_load_claim(R.csr, R.ws, R.ids, rq, d_w.p + q0, d_hops.p + q0, acc,
                                      d_cnt.p, st));
@@ -4480,10 +4711,9 @@ int64_t load_replay(Topology* top, const std::vector<int32_t>& sv, const std::ve
         }
         HIPCHK(hipEventRecord(R.ev.e[2], st));
         HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipEventElapsedTime(&ms, R.ev.e[0], R.ev.e[1]));
-        ls->replay_ms += ms;
-        HIPCHK(hipEventElapsedTime(&ms, R.ev.e[1], R.ev.e[2]));
-        ls->load_kernel_ms += ms;
+        for (int i = 0; i < LD_COUNT; i++) pcnt[i] += c[i];
+        r = chunk_times(R, &ls->replay_ms, &ls->load_kernel_ms);
+        if (r) return r;
         ls->chunks++;
     }
 
@@ -4497,6 +4727,7 @@ int64_t load_replay(Topology* top, const std::vector<int32_t>& sv, const std::ve
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipEventElapsedTime(&ms, R.ev.e[0], R.ev.e[1]));
     ls->load_kernel_ms += ms;
+    for (int i = 0; i < LD_COUNT; i++) cnt[i] += pcnt[i];
     ls->routed = (int64_t)cnt[LD_ROUTED];
     ls->broken = (int64_t)cnt[LD_BROKEN];
     ls->hop_weight = cnt[LD_HOPW];

@@ -300,6 +300,20 @@ hipError_t launch_sssp_batch(int K, const DevCSR& g, const SlotWs& ws, const uin
                              double delta, const SsspLdsPlan& plan, uint32_t iter_guard,
                              double2* out_lr, uint16_t* out_hops, double* out_rowmin,
                              unsigned long long* d_stats, hipStream_t stream);
+// The keep launch (sssp_batch_kernel<K, DIR, true>): block b runs batch b = positions [b kf,
+// b kf + kf) once in slot b, so (nsrc + kf - 1) / kf <= ws.slots; a bstart layout and btrace are
+// rejected.  SSSP, parent pass and epilogue are the build's (ws.rowflag[position], ST_ERRORS and
+// ST_LONGPATH in d_stats -- the caller's own block, zeroed by it), but no table is written.
+// Afterwards slot b's pair records tagged ep | kPairTagClaim, ep = (counters[4 b] - 1) %
+// kPairTagMask + 1, are the parent chains of batch b: lane j of vertex v at prec[slot][v K + j].
+hipError_t launch_sssp_batch_keep(int K, const DevCSR& g, const SlotWs& ws,
+                                  const uint32_t* d_sources, const double* d_srcsh, int nsrc, int kf,
+                                  const uint32_t* d_targets, int A, double delta,
+                                  const SsspLdsPlan& plan, uint32_t iter_guard,
+                                  unsigned long long* d_stats, hipStream_t stream);
+// tag word of a pair record (topo_sssp_batch.hip): the batch tag | claim bit of a resolved pair
+constexpr uint32_t kPairTagMask = 0x3FFFFFFFu;
+constexpr uint32_t kPairTagClaim = 0x40000000u;
 
 // Exact igraph-0.7 Dijkstra replay, one wavefront per row (topo_replay.hip): rows[0..nrows) index
 // d_sources / the output rows.  full = 1 ignores the early exit (test hook); dbg_dist / dbg_par
@@ -341,12 +355,26 @@ hipError_t launch_trace_edge_ids(int64_t V, int64_t E, int directed, const int32
 // The requests of one chunk of traced sources, sorted by source: request q has its source's
 // records in slot rslot[q], walks from rdst[q] back to rsrc[q] (relabelled ids) and belongs to
 // request ridx[q] of the call.
+// A chunk that ran the batch kernel's keep launch mixes two chain sources (topo_chain.h): rslot[q]
+// is then the source's index i within its chunk and rmap[i] (nmap entries) says where its chains
+// are -- the replay slot of a source the replay ran, kNoReplaySlot for a source whose chains are
+// the pair records of batch slot i / kf, lane i % kf (PairChains).  rmap == nullptr: every source
+// was replayed in slot rslot[q].
+constexpr uint32_t kNoReplaySlot = 0xFFFFFFFFu;
 struct TraceReqs {
     int64_t n = 0;
     const uint32_t* rslot = nullptr;
     const uint32_t* rsrc = nullptr;
     const uint32_t* rdst = nullptr;
     const uint32_t* ridx = nullptr;
+    const uint32_t* rmap = nullptr;
+    uint32_t nmap = 0;
+};
+// the batch slots' pair records after a keep launch of kf sources per batch (SlotWs)
+struct PairChains {
+    const uint4* prec = nullptr;
+    const uint32_t* counters = nullptr;
+    int slots = 0, K = 0, kf = 1;
 };
 // Pass 1: hops and status of every request into routes[ridx]; the entries it needs (hops + 1,
 // 0 when not traced) into lneed[q] (chunk order) and gneed[ridx] (request order).
@@ -358,6 +386,17 @@ hipError_t launch_route_trace_count(const ReplayCSR& g, const ReplayWs& ws, cons
 hipError_t launch_route_trace_write(const ReplayCSR& g, const ReplayWs& ws, const TraceIds& ids,
                                     const TraceReqs& rq, TraceRoute* routes, const int64_t* loff,
                                     int32_t* stV, int32_t* stE, hipStream_t stream);
+// The same two passes over the batch slots' pair records, for the requests whose rmap entry is
+// kNoReplaySlot (the replay's passes leave those alone and take the others).  Pass 1 also sets
+// broken[i] = 1 (one byte per chunk source, the caller's) for a source with a broken chain.
+// Routes of any length: the walk and its staging are in HBM, nothing depends on kMaxHops.
+hipError_t launch_route_trace_count_pairs(const ReplayCSR& g, const PairChains& pc,
+                                          const TraceReqs& rq, TraceRoute* routes, int64_t* lneed,
+                                          int64_t* gneed, uint8_t* broken, hipStream_t stream);
+hipError_t launch_route_trace_write_pairs(const ReplayCSR& g, const PairChains& pc,
+                                          const TraceIds& ids, const TraceReqs& rq,
+                                          TraceRoute* routes, const int64_t* loff, int32_t* stV,
+                                          int32_t* stE, hipStream_t stream);
 // out[i] = sum of in[0..i) for i < n (device exclusive scan)
 hipError_t trace_exclusive_scan(const int64_t* in, int64_t* out, int64_t n, hipStream_t stream);
 // offsets of the call: routes[i].offset = goff[i] when the route fits below cap entirely, else
@@ -390,6 +429,17 @@ hipError_t launch_load_validate(const ReplayCSR& g, const ReplayWs& ws, const Tr
 hipError_t launch_load_walk(const ReplayCSR& g, const ReplayWs& ws, const TraceIds& ids,
                             const TraceReqs& rq, const unsigned long long* w,
                             const int32_t* hops, const LoadAcc& acc, hipStream_t stream);
+// Validation and per-request walk over the batch slots' pair records (requests whose rmap entry is
+// kNoReplaySlot; broken[i] as launch_route_trace_count_pairs).  The tree accumulation below keeps
+// its state in the replay slots' vertex-record words, so it has no pair-record form: a call with
+// option "load_walk" = 0 replays every source.
+hipError_t launch_load_validate_pairs(const ReplayCSR& g, const PairChains& pc, const TraceReqs& rq,
+                                      const unsigned long long* w, int32_t* hops,
+                                      unsigned long long* cnt, uint8_t* broken,
+                                      hipStream_t stream);
+hipError_t launch_load_walk_pairs(const ReplayCSR& g, const PairChains& pc, const TraceIds& ids,
+                                  const TraceReqs& rq, const unsigned long long* w,
+                                  const int32_t* hops, const LoadAcc& acc, hipStream_t stream);
 // Tree accumulation.  The slots' vertex records are reused once the validation is over: the dist
 // words become the u64 weight of the vertex's subtree, the heap-position word {bit 31: visited,
 // bits 0..30: pending children}; reset clears both for the first nslots slots (the parent slot

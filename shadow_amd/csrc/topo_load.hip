@@ -4,7 +4,10 @@
 // weight) flows, the weight crossing every edge (forward and reverse half) and arriving at every
 // vertex of the route shdtopo_trace_routes reports.  As for a trace, the heap replay's trace
 // launch (topo_replay.hip) leaves igraph's parent of every popped vertex in the slot's vertex
-// records; the kernels here walk those chains.
+// records; the kernels here walk those chains.  The validation and the per-request walk also run
+// over the batch slots' pair records (their <true> forms, topo_chain.h) for the sources a keep
+// launch of the batch kernel serves; the tree accumulation keeps its state in the replay slots'
+// vertex-record words, so a call with option "load_walk" = 0 replays every source.
 //
 // All routes of one source share their first hops: a walk per request with one atomic per hop
 // puts a whole wavefront on the addresses next to the source.  Per source the union of the
@@ -45,7 +48,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "topo_dev_common.h"
+#include "topo_chain.h"
 
 namespace shdtopo {
 
@@ -66,9 +69,6 @@ unsigned grid_for(int64_t n) {
     return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + kTB - 1) / kTB, 65536));
 }
 
-__device__ __forceinline__ bool rec_reached(const uint4& x, int intKeys) {
-    return intKeys ? x.x != 0xFFFFFFFFu : __hiloint2double((int)x.y, (int)x.x) >= 0.0;
-}
 __device__ __forceinline__ u64* acc_of(uint4* vr, uint32_t v) {
     return reinterpret_cast<u64*>(vr + v);
 }
@@ -97,33 +97,42 @@ __device__ __forceinline__ void charge_self(const TraceIds& ids, const LoadAcc& 
     atomicAdd(&a.vload[src], w);
 }
 
+// PAIR: the chains are the batch slots' pair records (topo_chain.h); the validation then marks
+// the chunk sources that have a broken chain (broken[i] = 1: the host replays them)
+template <bool PAIR>
 __global__ void __launch_bounds__(kTB)
-load_validate_kernel(ReplayCSR g, ReplayWs ws, TraceReqs rq, const u64* __restrict__ w,
-                     int32_t* __restrict__ hops, u64* __restrict__ cnt) {
+load_validate_kernel(ReplayCSR g, ReplayWs ws, PairChains pc, TraceReqs rq,
+                     const u64* __restrict__ w, int32_t* __restrict__ hops, u64* __restrict__ cnt,
+                     uint8_t* __restrict__ broken) {
     const size_t V = (size_t)g.V;
     u64 nok = 0, nbad = 0, hw = 0;
     for (int64_t q = gtid(); q < rq.n; q += gstride()) {
         const uint32_t slot = rq.rslot[q], src = rq.rsrc[q], t = rq.rdst[q];
-        const bool inr = req_in_range(g, ws, slot, src, t);
-        const uint4* vr = ws.vrec + (size_t)(inr ? slot : 0u) * V;
+        Chain<PAIR> c;
+        const int st = c.open(g, ws, pc, rq, slot, src, t);
+        if (st == kChainSkip) continue;
+        const bool inr = st == kChainOk;
         int64_t h = -1;
         if (inr && t == src) {
             if (!isnan(g.selfLat[src])) h = 1;  // the self loop
         } else if (inr) {
-            bool bad = !rec_reached(vr[t], g.intKeys);
+            bool bad = !c.reached(g, t);
             uint32_t v = t;
             h = 0;
             while (!bad && v != src) {
-                const uint32_t j = vr[v].z;
-                if ((int64_t)j >= g.nadj) {
+                uint32_t p = 0, j = 0;
+                if (!c.template up<false>(g, TraceIds{}, v, p, j)) {
                     bad = true;
                     break;
                 }
                 h++;
-                v = g.own[j];
-                if (h > (int64_t)V || v >= (uint32_t)V) bad = true;
+                v = p;
+                if (h > (int64_t)V) bad = true;
             }
-            if (bad) h = -1;
+            if (bad) {
+                h = -1;
+                if (PAIR) broken[slot] = 1;
+            }
         }
         hops[q] = (int32_t)h;
         if (h < 0) {
@@ -144,27 +153,25 @@ load_validate_kernel(ReplayCSR g, ReplayWs ws, TraceReqs rq, const u64* __restri
     }
 }
 
+template <bool PAIR>
 __global__ void __launch_bounds__(kTB)
-load_walk_kernel(ReplayCSR g, ReplayWs ws, TraceIds ids, TraceReqs rq, const u64* __restrict__ w,
-                 const int32_t* __restrict__ hops, LoadAcc a) {
-    const size_t V = (size_t)g.V;
+load_walk_kernel(ReplayCSR g, ReplayWs ws, PairChains pc, TraceIds ids, TraceReqs rq,
+                 const u64* __restrict__ w, const int32_t* __restrict__ hops, LoadAcc a) {
     for (int64_t q = gtid(); q < rq.n; q += gstride()) {
+        const uint32_t slot = rq.rslot[q], src = rq.rsrc[q], t = rq.rdst[q];
+        Chain<PAIR> c;
+        if (c.open(g, ws, pc, rq, slot, src, t) != kChainOk) continue;
         int64_t h = hops[q];
         if (h < 1) continue;
-        const uint32_t slot = rq.rslot[q], src = rq.rsrc[q], t = rq.rdst[q];
-        if (!req_in_range(g, ws, slot, src, t)) continue;
         const u64 wq = w[q];
         if (t == src) {
             charge_self(ids, a, src, wq);
             continue;
         }
-        const uint4* vr = ws.vrec + (size_t)slot * V;
         uint32_t v = t;
         while (v != src && h-- > 0) {  // (the validation counted h hops)
-            const uint32_t j = vr[v].z;
-            if ((int64_t)j >= g.nadj) break;
-            const uint32_t p = g.own[j];
-            if (p >= (uint32_t)V) break;
+            uint32_t p = 0, j = 0;
+            if (!c.template up<true>(g, ids, v, p, j)) break;
             charge_hop(ids, a, j, p, v, wq);
             v = p;
         }
@@ -259,8 +266,20 @@ hipError_t launch_load_validate(const ReplayCSR& g, const ReplayWs& ws, const Tr
                                 const unsigned long long* w, int32_t* hops,
                                 unsigned long long* cnt, hipStream_t stream) {
     if (rq.n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(load_validate_kernel, dim3(grid_for(rq.n)), dim3(kTB), 0, stream, g, ws, rq,
-                       w, hops, cnt);
+    hipLaunchKernelGGL(load_validate_kernel<false>, dim3(grid_for(rq.n)), dim3(kTB), 0, stream, g,
+                       ws, PairChains{}, rq, w, hops, cnt, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_load_validate_pairs(const ReplayCSR& g, const PairChains& pc, const TraceReqs& rq,
+                                      const unsigned long long* w, int32_t* hops,
+                                      unsigned long long* cnt, uint8_t* broken,
+                                      hipStream_t stream) {
+    if (rq.n <= 0) return hipSuccess;
+    if (!rq.rmap || !broken || !pc.prec || !pc.counters || pc.kf < 1 || pc.kf > pc.K)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(load_validate_kernel<true>, dim3(grid_for(rq.n)), dim3(kTB), 0, stream, g,
+                       ReplayWs{}, pc, rq, w, hops, cnt, broken);
     return hipGetLastError();
 }
 
@@ -268,8 +287,19 @@ hipError_t launch_load_walk(const ReplayCSR& g, const ReplayWs& ws, const TraceI
                             const TraceReqs& rq, const unsigned long long* w,
                             const int32_t* hops, const LoadAcc& acc, hipStream_t stream) {
     if (rq.n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(load_walk_kernel, dim3(grid_for(rq.n)), dim3(kTB), 0, stream, g, ws, ids,
-                       rq, w, hops, acc);
+    hipLaunchKernelGGL(load_walk_kernel<false>, dim3(grid_for(rq.n)), dim3(kTB), 0, stream, g, ws,
+                       PairChains{}, ids, rq, w, hops, acc);
+    return hipGetLastError();
+}
+
+hipError_t launch_load_walk_pairs(const ReplayCSR& g, const PairChains& pc, const TraceIds& ids,
+                                  const TraceReqs& rq, const unsigned long long* w,
+                                  const int32_t* hops, const LoadAcc& acc, hipStream_t stream) {
+    if (rq.n <= 0) return hipSuccess;
+    if (!rq.rmap || !pc.prec || !pc.counters || pc.kf < 1 || pc.kf > pc.K)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(load_walk_kernel<true>, dim3(grid_for(rq.n)), dim3(kTB), 0, stream, g,
+                       ReplayWs{}, pc, ids, rq, w, hops, acc);
     return hipGetLastError();
 }
 

@@ -284,6 +284,7 @@ struct BBuckets {
 // nothing, so no per-batch clearing is needed.
 constexpr uint32_t kTagMask = 0x3FFFFFFFu;
 constexpr uint32_t kTagClaim = 0x40000000u;
+static_assert(kTagMask == kPairTagMask && kTagClaim == kPairTagClaim, "the pair walks' tag (topo_device.h)");
 constexpr uint32_t kTagTie = 0x80000000u;
 __device__ __forceinline__ bool tag_claimed(uint32_t w, uint32_t ep) {
     return (w & ~kTagTie) == (ep | kTagClaim);
@@ -929,7 +930,12 @@ constexpr uint32_t kNoPairS = 0xFFFFFFFFu;
 
 // DIR: a directed topology (parents from the in-rows, DevCSR::rowptr_in); a separate
 // instantiation, so the undirected kernel's code and registers are those of round 5 before it.
-template <int K, bool DIR>
+// KEEP: the trace launch (launch_sssp_batch_keep).  Block b runs batch b, and only that one, in
+// slot b, so the slot's pair records with tag ep | kTagClaim are still the batch's chains when the
+// kernel ends (a dequeue loop would let a fast workgroup take a second batch over them).  The
+// epilogue walks every target as in a build -- row flags, ST_ERRORS, ST_LONGPATH -- but its table
+// stores are compiled out.  The KEEP = false instantiations are the build's, unchanged.
+template <int K, bool DIR, bool KEEP = false>
 __global__ void __launch_bounds__(kSsspBlock, kBatchWgPerCu)
 sssp_batch_kernel(DevCSR g, SlotWs ws, const uint32_t* __restrict__ sources,
                   const double* __restrict__ srcsh, int nsrc, int kf,
@@ -1263,9 +1269,9 @@ sssp_batch_kernel(DevCSR g, SlotWs ws, const uint32_t* __restrict__ sources,
                     }
                     const size_t ob = (size_t)(ws.rowmap ? (int)ws.rowmap[r0v + jj] : (int)(r0v + jj)) * (size_t)A + k;
                     const uint16_t hh = (uint16_t)(hcnt > 65535u ? 65535u : hcnt);
-                    wl_count(L, WL_OUT, true, out_lr + ob);
-                    wl_count(L, WL_OUT, true, out_hops + ob);
-                    {  // the table (1.8 GB per launch) is not re-read by the kernel: nontemporal
+                    wl_count(L, WL_OUT, !KEEP, out_lr + ob);
+                    wl_count(L, WL_OUT, !KEEP, out_hops + ob);
+                    if (!KEEP) {  // the table (1.8 GB per launch) is not re-read by the kernel: nontemporal
                         typedef double f64x2 __attribute__((ext_vector_type(2)));
                         const f64x2 r2 = {lat, rel};
                         __builtin_nontemporal_store(r2, reinterpret_cast<f64x2*>(out_lr) + ob);
@@ -1278,10 +1284,12 @@ sssp_batch_kernel(DevCSR g, SlotWs ws, const uint32_t* __restrict__ sources,
     };
 
     for (;;) {
-        if (tid == 0) L.idx = (uint32_t)atomicAdd(&stats[ST_DEQUEUE], 1ull);
-        __syncthreads();
-        const uint32_t bidx = L.idx;
-        __syncthreads();
+        if (!KEEP) {
+            if (tid == 0) L.idx = (uint32_t)atomicAdd(&stats[ST_DEQUEUE], 1ull);
+            __syncthreads();
+        }
+        const uint32_t bidx = KEEP ? blockIdx.x : L.idx;
+        if (!KEEP) __syncthreads();
         // batch bidx: sources [bidx kf, bidx kf + kf) in lanes 0..nk-1 (kf <= K: the host fills
         // batches below K when that finishes the sources in fewer rounds of the slots), or the
         // host's layout [bstart[bidx], bstart[bidx + 1]) sized by measured costs
@@ -2094,6 +2102,7 @@ sssp_batch_kernel(DevCSR g, SlotWs ws, const uint32_t* __restrict__ sources,
             b[6] = L.cnt[0] - b[6];
             b[7] = (unsigned long long)nk;
         }
+        if (KEEP) break;  // one batch per block: its records stay
     }
     __syncthreads();
     if (tid == 0) {
@@ -2669,6 +2678,43 @@ hipError_t launch_sssp_batch(int K, const DevCSR& g, const SlotWs& ws, const uin
         case 4: return launch_batch_k<4>(g, ws, d_sources, d_srcsh, nsrc, kf, d_targets, A, delta, plan, iter_guard, out_lr, out_hops, out_rowmin, d_stats, stream);
         case 8: return launch_batch_k<8>(g, ws, d_sources, d_srcsh, nsrc, kf, d_targets, A, delta, plan, iter_guard, out_lr, out_hops, out_rowmin, d_stats, stream);
         case 16: return launch_batch_k<16>(g, ws, d_sources, d_srcsh, nsrc, kf, d_targets, A, delta, plan, iter_guard, out_lr, out_hops, out_rowmin, d_stats, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+template <int K>
+static hipError_t launch_keep_k(const DevCSR& g, const SlotWs& ws, const uint32_t* d_sources,
+                                const double* d_srcsh, int nsrc, int kf, const uint32_t* d_targets,
+                                int A, double delta, const SsspLdsPlan& plan, uint32_t iter_guard,
+                                unsigned long long* d_stats, hipStream_t stream) {
+    if (kf < 1 || kf > K || nsrc < 0 || A < 0) return hipErrorInvalidValue;
+    if (ws.bstart || ws.btrace || !ws.rowflag || !d_stats) return hipErrorInvalidValue;
+    const int nb = (nsrc + kf - 1) / kf;
+    if (nb < 1) return hipSuccess;
+    if (nb > ws.slots) return hipErrorInvalidValue;  // block b keeps slot b to itself
+    if ((int64_t)plan.H > g.V || plan.P > plan.H || plan.bytes > kBMaxLds ||
+        blayout<K>(plan.H, plan.P).bytes != plan.bytes || ws.K != K)
+        return hipErrorInvalidValue;
+    auto* kern = g.directed ? sssp_batch_kernel<K, true, true> : sssp_batch_kernel<K, false, true>;
+    hipError_t e = hipFuncSetAttribute((const void*)kern,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBMaxLds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(nb), dim3(kSsspBlock), plan.bytes, stream, g, ws, d_sources,
+                       d_srcsh, nsrc, kf, d_targets, A, delta, plan.H, plan.P, iter_guard,
+                       (double2*)nullptr, (uint16_t*)nullptr, (double*)nullptr, d_stats);
+    return hipGetLastError();
+}
+
+hipError_t launch_sssp_batch_keep(int K, const DevCSR& g, const SlotWs& ws,
+                                  const uint32_t* d_sources, const double* d_srcsh, int nsrc, int kf,
+                                  const uint32_t* d_targets, int A, double delta,
+                                  const SsspLdsPlan& plan, uint32_t iter_guard,
+                                  unsigned long long* d_stats, hipStream_t stream) {
+    switch (K) {
+        case 2: return launch_keep_k<2>(g, ws, d_sources, d_srcsh, nsrc, kf, d_targets, A, delta, plan, iter_guard, d_stats, stream);
+        case 4: return launch_keep_k<4>(g, ws, d_sources, d_srcsh, nsrc, kf, d_targets, A, delta, plan, iter_guard, d_stats, stream);
+        case 8: return launch_keep_k<8>(g, ws, d_sources, d_srcsh, nsrc, kf, d_targets, A, delta, plan, iter_guard, d_stats, stream);
+        case 16: return launch_keep_k<16>(g, ws, d_sources, d_srcsh, nsrc, kf, d_targets, A, delta, plan, iter_guard, d_stats, stream);
     }
     return hipErrorInvalidValue;
 }

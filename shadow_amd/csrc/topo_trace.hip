@@ -5,7 +5,10 @@
 // (:594,644,654-656).  The table kernels walk the same chains and keep {lat, rel, hops} only.
 // Here the chains are written out: the heap replay (topo_replay.hip, its trace launch) leaves
 // igraph's parent of every popped vertex in the slot's vertex records, and route_trace_kernel
-// walks them for the requested (source, destination) pairs.
+// walks them for the requested (source, destination) pairs.  A source whose row the batch kernel's
+// keep launch (topo_sssp_batch.hip) leaves unflagged needs no replay: the same walk runs over the
+// batch slot's pair records instead (route_trace_kernel<PASS, true>; topo_chain.h has the two
+// chain sources), finding each hop's replay-CSR entry by a binary search of the parent's row.
 //
 //   pass 1  one thread per request walks destination -> source and counts the hops, with the
 //           replay epilogue's guards (unreached vertex, slot out of range, more than V hops);
@@ -18,7 +21,7 @@
 //   place + scatter  routes that fit below the caller's cap get their offset and are copied from
 //           staging to the output arrays (one wavefront per route).
 // Every store is a plain vector store into memory the call owns.  The walks are dependent random
-// 16-B loads, a few per hop: microseconds next to the replay that precedes them.
+// 16-B loads, a few per hop: microseconds next to the replay or the keep launch before them.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -26,7 +29,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "topo_dev_common.h"
+#include "topo_chain.h"
 
 namespace shdtopo {
 
@@ -44,30 +47,8 @@ unsigned grid_for(int64_t n) {
     return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + kTB - 1) / kTB, 65536));
 }
 
-// a vertex record's dist says reached (RpKey::reached of topo_replay.hip, both key encodings)
-__device__ __forceinline__ bool rec_reached(const uint4& x, int intKeys) {
-    return intKeys ? x.x != 0xFFFFFFFFu : __hiloint2double((int)x.y, (int)x.x) >= 0.0;
-}
-
 __global__ void trace_fill_i32_kernel(int32_t* __restrict__ p, int32_t v, int64_t n) {
     for (int64_t i = gtid(); i < n; i += gstride()) p[i] = v;
-}
-
-// entry of row x (relabelled) whose neighbour has ORIGINAL id y: rows ascend by original
-// neighbour id (igraph_incident order), one entry per neighbour (parallel groups merged)
-__device__ __forceinline__ int64_t find_entry(const uint32_t* __restrict__ rowptr,
-                                              const uint4* __restrict__ rec,
-                                              const int32_t* __restrict__ perm, uint32_t x,
-                                              int32_t y) {
-    uint32_t lo = rowptr[x], hi = rowptr[x + 1];
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        const int32_t o = perm[rec[mid].x];
-        if (o == y) return (int64_t)mid;
-        if (o < y) lo = mid + 1;
-        else hi = mid;
-    }
-    return -1;
 }
 
 __global__ void trace_edge_id_kernel(int64_t V, int64_t E, int directed,
@@ -90,38 +71,46 @@ __global__ void trace_edge_id_kernel(int64_t V, int64_t E, int directed,
     }
 }
 
-// PASS 1: count; PASS 2: write.  One thread per request of the chunk.
-template <int PASS>
+// PASS 1: count; PASS 2: write.  One thread per request of the chunk.  PAIR: the chains are the
+// batch slots' pair records (topo_chain.h); pass 1 then also marks the chunk sources that have a
+// broken chain (broken[i] = 1: the host replays them).
+template <int PASS, bool PAIR>
 __global__ void __launch_bounds__(kTB)
-route_trace_kernel(ReplayCSR g, ReplayWs ws, TraceIds ids, TraceReqs rq,
+route_trace_kernel(ReplayCSR g, ReplayWs ws, PairChains pc, TraceIds ids, TraceReqs rq,
                    TraceRoute* __restrict__ routes, int64_t* __restrict__ lneed,
                    int64_t* __restrict__ gneed, const int64_t* __restrict__ loff,
-                   int32_t* __restrict__ stV, int32_t* __restrict__ stE) {
+                   int32_t* __restrict__ stV, int32_t* __restrict__ stE,
+                   uint8_t* __restrict__ broken) {
     const size_t V = (size_t)g.V;
     for (int64_t q = gtid(); q < rq.n; q += gstride()) {
         const uint32_t slot = rq.rslot[q], src = rq.rsrc[q], t = rq.rdst[q], idx = rq.ridx[q];
-        const bool inr = slot < (uint32_t)ws.slots && src < (uint32_t)V && t < (uint32_t)V;
-        const uint4* vr = ws.vrec + (size_t)(inr ? slot : 0u) * V;
+        Chain<PAIR> c;
+        const int st = c.open(g, ws, pc, rq, slot, src, t);
+        if (st == kChainSkip) continue;
+        const bool inr = st == kChainOk;
         if (PASS == 1) {
             int64_t h = -1;
             if (inr && t == src) {
                 // path [src]: the self loop (the helper's nVertices == 1 branch)
                 if (!isnan(g.selfLat[src])) h = 1;
             } else if (inr) {
-                bool bad = !rec_reached(vr[t], g.intKeys);
+                bool bad = !c.reached(g, t);
                 uint32_t v = t;
                 h = 0;
                 while (!bad && v != src) {
-                    const uint32_t j = vr[v].z;
-                    if ((int64_t)j >= g.nadj) {
+                    uint32_t p = 0, j = 0;
+                    if (!c.template up<false>(g, ids, v, p, j)) {
                         bad = true;
                         break;
                     }
                     h++;
-                    v = g.own[j];
-                    if (h > (int64_t)V || v >= (uint32_t)V) bad = true;
+                    v = p;
+                    if (h > (int64_t)V) bad = true;
                 }
-                if (bad) h = -1;
+                if (bad) {
+                    h = -1;
+                    if (PAIR) broken[slot] = 1;
+                }
             }
             TraceRoute r;
             r.offset = -1;
@@ -155,10 +144,9 @@ route_trace_kernel(ReplayCSR g, ReplayWs ws, TraceIds ids, TraceReqs rq,
                 stV[base + h] = ids.perm[t];
                 stE[base + h] = -1;
                 for (int64_t k = h - 1; k >= 0; --k) {
-                    const uint32_t j = vr[v].z;
-                    if ((int64_t)j >= g.nadj) break;  // (pass 1 validated the chain)
-                    v = g.own[j];
-                    if (v >= (uint32_t)V) break;
+                    uint32_t p = 0, j = 0;
+                    if (!c.template up<true>(g, ids, v, p, j)) break;  // (pass 1 validated the chain)
+                    v = p;
                     stV[base + k] = ids.perm[v];
                     stE[base + k] = (int32_t)j;
                 }
@@ -233,8 +221,21 @@ hipError_t launch_route_trace_count(const ReplayCSR& g, const ReplayWs& ws, cons
                                     TraceRoute* routes, int64_t* lneed, int64_t* gneed,
                                     hipStream_t stream) {
     if (rq.n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(route_trace_kernel<1>, dim3(grid_for(rq.n)), dim3(kTB), 0, stream, g, ws,
-                       TraceIds{}, rq, routes, lneed, gneed, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL((route_trace_kernel<1, false>), dim3(grid_for(rq.n)), dim3(kTB), 0, stream,
+                       g, ws, PairChains{}, TraceIds{}, rq, routes, lneed, gneed, nullptr, nullptr,
+                       nullptr, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_route_trace_count_pairs(const ReplayCSR& g, const PairChains& pc,
+                                          const TraceReqs& rq, TraceRoute* routes, int64_t* lneed,
+                                          int64_t* gneed, uint8_t* broken, hipStream_t stream) {
+    if (rq.n <= 0) return hipSuccess;
+    if (!rq.rmap || !broken || !pc.prec || !pc.counters || pc.kf < 1 || pc.kf > pc.K)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL((route_trace_kernel<1, true>), dim3(grid_for(rq.n)), dim3(kTB), 0, stream,
+                       g, ReplayWs{}, pc, TraceIds{}, rq, routes, lneed, gneed, nullptr, nullptr,
+                       nullptr, broken);
     return hipGetLastError();
 }
 
@@ -242,8 +243,22 @@ hipError_t launch_route_trace_write(const ReplayCSR& g, const ReplayWs& ws, cons
                                     const TraceReqs& rq, TraceRoute* routes, const int64_t* loff,
                                     int32_t* stV, int32_t* stE, hipStream_t stream) {
     if (rq.n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(route_trace_kernel<2>, dim3(grid_for(rq.n)), dim3(kTB), 0, stream, g, ws,
-                       ids, rq, routes, nullptr, nullptr, loff, stV, stE);
+    hipLaunchKernelGGL((route_trace_kernel<2, false>), dim3(grid_for(rq.n)), dim3(kTB), 0, stream,
+                       g, ws, PairChains{}, ids, rq, routes, nullptr, nullptr, loff, stV, stE,
+                       nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_route_trace_write_pairs(const ReplayCSR& g, const PairChains& pc,
+                                          const TraceIds& ids, const TraceReqs& rq,
+                                          TraceRoute* routes, const int64_t* loff, int32_t* stV,
+                                          int32_t* stE, hipStream_t stream) {
+    if (rq.n <= 0) return hipSuccess;
+    if (!rq.rmap || !pc.prec || !pc.counters || pc.kf < 1 || pc.kf > pc.K)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL((route_trace_kernel<2, true>), dim3(grid_for(rq.n)), dim3(kTB), 0, stream,
+                       g, ReplayWs{}, pc, ids, rq, routes, nullptr, nullptr, loff, stV, stE,
+                       nullptr);
     return hipGetLastError();
 }
 

@@ -11,7 +11,13 @@ same requests on the same box a third line gives the trace (shdtopo_trace_routes
 time of its kernels -- the existing code the accumulation is compared against.  The two modes'
 arrays are compared with each other (a dry check; the tests compare with the oracle).
 
+With --batch 1 or both the table is built first and every call runs with option trace_batch as
+asked (both: 0 then 1 -- the replay path and the batch path in one process on one box); the lines
+then carry the keep launches' event time and the sources served from pair records.  --batch 0
+(the default) is the probe as it was: no table, replay only.
+
 usage: python tools/load_probe.py [--integer] [--sources N] [--matrix-sources N] [--small]
+                                  [--batch 0|1|both]
   --integer         C4-int (latencies U{1..100}: u32 heap keys) instead of C4
   --sources         distinct sources of case (c), default 5000
   --matrix-sources  sources of case (b), default 256
@@ -35,7 +41,9 @@ def main():
     ap.add_argument("--sources", type=int, default=5000)
     ap.add_argument("--matrix-sources", type=int, default=256)
     ap.add_argument("--small", action="store_true")
+    ap.add_argument("--batch", choices=["0", "1", "both"], default="0")
     args = ap.parse_args()
+    modes = {"0": [0], "1": [1], "both": [0, 1]}[args.batch]
     import torch
     if not torch.cuda.is_available():
         sys.exit("load_probe needs the GPU: a link load of an SSSP topology runs the heap replay")
@@ -47,15 +55,22 @@ def main():
     else:
         top = sa.Topology.synthetic(seed=20261015, integer_latency=args.integer)
         hosts = 100_000
-    # the batched SSSP's workspace is not needed here: its HBM goes to the replay's slots
-    top.set_option("prepare_on_attach", 0)
+    # replay only: the batched SSSP's workspace is not needed, its HBM goes to the replay's slots
+    if modes == [0]:
+        top.set_option("prepare_on_attach", 0)
     top.synth_packets(20261015, hosts, 1000, 10**9, 10**7)  # host k < poi count sits on poi k
     A = len(top.attached_vertices())
+    build_s = None
+    if modes != [0]:
+        t1 = time.time()
+        top.build()
+        build_s = round(time.time() - t1, 2)
     ips = np.asarray([sa.ip_to_network("11.%d.%d.%d" % ((k + 1) >> 16 & 255, (k + 1) >> 8 & 255,
                                                        (k + 1) & 255)) for k in range(A)], np.uint32)
     print(json.dumps({"topology": "C4-int" if args.integer else "C4", "small": args.small,
                       "vertices": top.num_vertices, "edges": top.num_edges, "attached": A,
-                      "setup_s": round(time.time() - t0, 2)}), flush=True)
+                      "table_build_s": build_s, "setup_s": round(time.time() - t0, 2)}),
+          flush=True)
     nsrc = min(args.sources, A - 1)
     msrc = min(args.matrix_sources, A)
     rng = np.random.default_rng(1)
@@ -77,15 +92,18 @@ def main():
     for name, s, d in cases:
         w = rng.integers(1, 1449, len(s)).astype(np.uint64)  # payload bytes
         outs = []
-        for walk in (0, 1):
+        for walk, mode in [(wk, m) for wk in (0, 1) for m in modes]:
             top.set_option("load_walk", walk)
+            top.set_option("trace_batch", mode)
             t1 = time.time()
             out = top.link_load(s, d, w)
             wall = time.time() - t1
             ls = top.link_load_stats()
             outs.append(out)
             print(json.dumps({
-                "case": name, "load_walk": walk, "requests": int(len(s)),
+                "case": name, "load_walk": walk, "trace_batch": mode, "requests": int(len(s)),
+                "batch_sources": ls["batch_sources"], "batch_fallback": ls["batch_fallback"],
+                "batch_ms": round(ls["batch_ms"], 3),
                 "sources": ls["sources"], "chunks": ls["chunks"], "routed": ls["routed"],
                 "broken": ls["broken"], "tree_vertices": ls["tree_vertices"],
                 "hop_weight": ls["hop_weight"],
@@ -97,19 +115,24 @@ def main():
                 "load_kernel_share": round(ls["load_kernel_ms"] / max(ls["total_ms"], 1e-9), 6),
             }), flush=True)
         top.set_option("load_walk", 0)
-        same = all(np.array_equal(outs[0][k], outs[1][k]) for k in ("edge_fwd", "edge_rev", "vertex"))
-        t1 = time.time()
-        tr = top.trace_routes(s, d, cap=16 * len(s))  # one call: no sizing pass
-        wall = time.time() - t1
-        ts = top.trace_stats()
-        print(json.dumps({
-            "case": name, "trace": True, "modes_agree": bool(same), "requests": int(len(s)),
-            "entries": int(tr["total"]), "not_written": int((tr["status"] != 0).sum()),
-            "python_wall_s": round(wall, 4),
-            "total_ms": round(ts["total_ms"], 3),
-            "replay_ms": round(ts["replay_ms"], 3),
-            "trace_kernel_ms": round(ts["trace_kernel_ms"], 3),
-        }), flush=True)
+        same = all(np.array_equal(outs[0][k], o[k]) for o in outs[1:]
+                   for k in ("edge_fwd", "edge_rev", "vertex"))
+        for mode in modes:
+            top.set_option("trace_batch", mode)
+            t1 = time.time()
+            tr = top.trace_routes(s, d, cap=16 * len(s))  # one call: no sizing pass
+            wall = time.time() - t1
+            ts = top.trace_stats()
+            print(json.dumps({
+                "case": name, "trace": True, "trace_batch": mode, "modes_agree": bool(same),
+                "batch_sources": ts["batch_sources"], "batch_fallback": ts["batch_fallback"],
+                "batch_ms": round(ts["batch_ms"], 3), "requests": int(len(s)),
+                "entries": int(tr["total"]), "not_written": int((tr["status"] != 0).sum()),
+                "python_wall_s": round(wall, 4),
+                "total_ms": round(ts["total_ms"], 3),
+                "replay_ms": round(ts["replay_ms"], 3),
+                "trace_kernel_ms": round(ts["trace_kernel_ms"], 3),
+            }), flush=True)
 
 
 if __name__ == "__main__":
