@@ -398,6 +398,9 @@ typedef struct {
                                    rows to the end of the exchange (the part of exchange_ms no
                                    kernel hid; exchange_kind 2 overlaps the slower shards) */
     int64_t workspace_bytes;    /* HBM held by the batched SSSP's workspace (all slots) */
+    int64_t peeled_targets;     /* the last batched build: targets with one non-loop edge, resolved
+                                   from their uplink instead of the graph search (option
+                                   "leaf_targets"; 0 when off or the topology is directed) */
 } ShdStats;
 int shdtopo_get_stats(Topology* top, ShdStats* out);
 

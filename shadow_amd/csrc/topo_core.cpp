@@ -366,6 +366,12 @@ struct _Topology {
                               // into non-target tail vertices that would expand nothing are
                               // dropped (topo_sssp_batch.hip)
     std::vector<uint32_t> adjkTargets;  // the target set whose bits d_adjk carries
+    bool leafTargets = true;   // option "leaf_targets": a target with one non-loop edge is resolved
+                               // from its uplink (undirected topologies; topo_sssp_batch.hip)
+    bool adjkLeaf = false;     // d_adjk's target-derived content is that of the effective target
+                               // set: (adjkTargets - peeled) + uplinks, peeled vertices dead
+    std::vector<uint32_t> leafFor;  // the target set d_tleaf / d_tbitsEff / d_dead belong to
+    int64_t leafPeeled = 0;         // ... and its peeled targets
     bool adjkFlagged = false;
     bool adjkPlain = false;    // d_adjk / d_kap / d_ksum / d_kap0 are the plain kappa-sorted copy
     bool adjkResorted = false; // ... re-sorted by the target-aware key of adjkTargets
@@ -438,6 +444,10 @@ struct _Topology {
     DevBuf<uint32_t> d_rown;
     DevBuf<double2> d_rhop;
     DevBuf<uint32_t> d_tbits;
+    // leaf targets (ensure_leaf_targets): the records, the effective target bitmap, the peeled
+    // vertices' bitmap, their count
+    DevBuf<uint4> d_tleaf;
+    DevBuf<uint32_t> d_tbitsEff, d_dead, d_leafCount;
     DevBuf<uint4> d_rvrec, d_rnode;
     DevBuf<uint32_t> d_rpath, d_rrows;
     DevBuf<uint8_t> d_rowflag;
@@ -997,7 +1007,9 @@ int upload_csr_impl(Topology* top) {
                              top->d_kap0.p, st));
     top->adjkPlain = true;
     top->adjkFlagged = false;
+    top->adjkLeaf = false;
     top->adjkTargets.clear();
+    top->leafFor.clear();
     top->rowsSorted = true;
     // the kappa fixpoint's static w - pi per out-row entry (the first target preparation's)
     HIPCHK(top->d_kfKap.ensure((size_t)std::max<int64_t>(1, nadj)));
@@ -1052,7 +1064,8 @@ DevCSR dev_csr(Topology* top) {
     c.selfLat = top->d_selfLat.p;
     c.selfLoss = top->d_selfLoss.p;
     c.rows_sorted = top->rowsSorted ? 1 : 0;
-    c.tflags = top->adjkFlagged && top->targetSkip ? 1 : 0;  // marks of the launch's target set
+    // marks of the launch's target set; 2: of the effective set, peeled leaf targets dead
+    c.tflags = top->adjkFlagged && top->targetSkip ? (top->adjkLeaf ? 2 : 1) : 0;
     return c;
 }
 
@@ -1338,6 +1351,38 @@ int upload_target_bits(Topology* top, const std::vector<uint32_t>& tgt, hipStrea
     HIPCHK(top->d_tbits.ensure(words));
     HIPCHK(hipMemcpyAsync(top->d_tbits.p, tb.data(), 4 * words, hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));  // tb must outlive the async copy
+    return 0;
+}
+
+// Option "leaf_targets" applies: undirected topologies only (a directed one keeps every target).
+bool leaf_targets_on(const Topology* top) { return top->leafTargets && !top->isDirected; }
+
+// The leaf-target records of target set tgt (d_tgt: the same set on the device), the effective
+// target bitmap and the peeled vertices' bitmap: one small kernel over the targets, run when the
+// set changed.
+int ensure_leaf_targets(Topology* top, const std::vector<uint32_t>& tgt, const uint32_t* d_tgt,
+                        hipStream_t st) {
+    if (top->leafFor == tgt && top->d_tleaf.p) return 0;
+    const size_t words = ((size_t)top->g.V + 31) / 32;
+    const size_t A = tgt.size();
+    std::vector<uint32_t> tb(words, 0u);
+    for (uint32_t t : tgt) tb[t >> 5] |= 1u << (t & 31u);
+    top->leafFor.clear();
+    HIPCHK(top->d_tleaf.ensure(2 * std::max<size_t>(1, A)));
+    HIPCHK(top->d_tbitsEff.ensure(words));
+    HIPCHK(top->d_dead.ensure(words));
+    HIPCHK(top->d_leafCount.ensure(1));
+    HIPCHK(hipMemcpyAsync(top->d_tbitsEff.p, tb.data(), 4 * words, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(top->d_dead.p, 0, 4 * words, st));
+    HIPCHK(hipMemsetAsync(top->d_leafCount.p, 0, 4, st));
+    HIPCHK(launch_leaf_targets(top->d_rowptr.p, top->d_adj.p, top->d_aloss.p, d_tgt, (int)A,
+                               top->d_tleaf.p, top->d_tbitsEff.p, top->d_dead.p,
+                               top->d_leafCount.p, st));
+    uint32_t n = 0;
+    HIPCHK(hipMemcpyAsync(&n, top->d_leafCount.p, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));  // tb and n must outlive the async copies
+    top->leafPeeled = (int64_t)n;
+    top->leafFor = tgt;
     return 0;
 }
 
@@ -1762,6 +1807,7 @@ int enqueue_rows(Topology* top, int64_t row0, int64_t row1, double2* out_lr, uin
         HIPCHK(hipMemcpyAsync(top->d_sources.p, src.data(), sizeof(uint32_t) * (size_t)rows, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(top->d_targets.p, tgt.data(), sizeof(uint32_t) * (size_t)A, hipMemcpyHostToDevice, st));
         const int K = batch_k(top);
+        top->stats.peeled_targets = 0;
         HIPCHK(hipEventRecord(top->ev0, st));
         if (!allReplay) {
             r = ensure_workspace(top, (int)rows);
@@ -1776,13 +1822,23 @@ int enqueue_rows(Topology* top, int64_t row0, int64_t row1, double2* out_lr, uin
             // would cut rows that lead to the new targets), then prepares the new set if the
             // target skip is on.
             const int64_t nadjk = (int64_t)(top->d_adjk.n / 4);
-            if (!top->adjkPlain && top->adjkTargets != tgt) {
+            // leaf targets: the records go with the launch, the copy's target-derived content
+            // with the effective set -- a copy prepared the other way is restored first
+            const bool leaf = leaf_targets_on(top);
+            if (leaf) {
+                r = ensure_leaf_targets(top, tgt, top->d_targets.p, st);
+                if (r) return r;
+                ws.tleaf = top->d_tleaf.p;
+            }
+            top->stats.peeled_targets = leaf ? top->leafPeeled : 0;
+            if (!top->adjkPlain && (top->adjkTargets != tgt || top->adjkLeaf != leaf)) {
                 HIPCHK(launch_kappa_copy(top->g.V, nadjk, hub_segs(top), top->d_rowptr.p, adj_out(top), top->d_pot.p,
                                          top->d_sptPar.p, top->d_adjk.p, top->d_kap.p,
                                          top->d_ksum.p, top->d_kap0.p, st));
                 top->adjkPlain = true;
                 top->adjkFlagged = false;
                 top->adjkResorted = false;
+                top->adjkLeaf = false;
                 top->adjkTargets.clear();
             }
             if (top->targetSkip && top->adjkPlain) {
@@ -1794,7 +1850,10 @@ int enqueue_rows(Topology* top, int64_t row0, int64_t row1, double2* out_lr, uin
                 r = upload_target_bits(top, tgt, st);
                 if (r) return r;
                 HIPCHK(hipEventRecord(top->evp0, st));
-                HIPCHK(launch_mark_targets(top->d_adjk.p, nadjk, top->d_tbits.p, st));
+                // (leaf targets: the effective set's bits, the peeled vertices dead)
+                const uint32_t* tbits = leaf ? top->d_tbitsEff.p : top->d_tbits.p;
+                const uint32_t* dead = leaf ? top->d_dead.p : nullptr;
+                HIPCHK(launch_mark_targets(top->d_adjk.p, nadjk, tbits, st));
                 // the records' kappa field: the target-aware fixpoint (kappa0 with 0 iterations)
                 const int64_t V = top->g.V;
                 const HubSegs hs = hub_segs(top);
@@ -1809,15 +1868,15 @@ int enqueue_rows(Topology* top, int64_t row0, int64_t row1, double2* out_lr, uin
                     top->kfKapReady = true;
                 }
                 HIPCHK(hipMemsetAsync(top->d_kfChanged.p, 0, sizeof(unsigned int) * ((size_t)nit + 1), st));
-                HIPCHK(launch_kfix_step(top->d_rowptr.p, adj_out(top), top->d_kfKap.p, top->d_tbits.p,
+                HIPCHK(launch_kfix_step(top->d_rowptr.p, adj_out(top), top->d_kfKap.p, tbits,
                                         nullptr, top->d_kfA.p, V, hs, top->d_kfPart.p,
-                                        top->d_kfChanged.p, st));
+                                        top->d_kfChanged.p, st, dead));
                 double* kin = top->d_kfA.p;
                 double* kout = top->d_kfB.p;
                 for (int it = 0; it < nit; it++) {
                     HIPCHK(launch_kfix_step(top->d_rowptr.p, adj_out(top), top->d_kfKap.p,
-                                            top->d_tbits.p, kin, kout, V, hs, top->d_kfPart.p,
-                                            top->d_kfChanged.p + 1 + it, st));
+                                            tbits, kin, kout, V, hs, top->d_kfPart.p,
+                                            top->d_kfChanged.p + 1 + it, st, dead));
                     std::swap(kin, kout);
                 }
                 if (top->targetResort) {
@@ -1826,13 +1885,14 @@ int enqueue_rows(Topology* top, int64_t row0, int64_t row1, double2* out_lr, uin
                     if (r) return r;
                     HIPCHK(launch_kprime_resort(top->d_adjk.p, top->d_kap.p, top->d_ksum.p,
                                                 top->d_kap0.p, top->d_rowptr.p, V, nadjk,
-                                                top->d_pot.p, top->d_tbits.p, kin, sc, st));
+                                                top->d_pot.p, tbits, kin, sc, st));
                 }
                 HIPCHK(launch_kfix_store(top->d_adjk.p, nadjk, kin, st));
                 HIPCHK(hipEventRecord(top->evp1, st));
                 top->tpPending = true;
                 top->adjkTargets = tgt;
                 top->adjkFlagged = true;
+                top->adjkLeaf = leaf;
                 top->adjkPlain = false;
                 top->adjkResorted = top->targetResort;
             }
@@ -2346,6 +2406,7 @@ void sync_peer(Topology* top, Topology* p) {
     p->targetSkip = top->targetSkip;
     p->targetKappa = top->targetKappa;
     p->targetResort = top->targetResort;
+    p->leafTargets = top->leafTargets;
     p->attached = top->attached;
     p->colOf = top->colOf;
     p->A = top->A;
@@ -2401,6 +2462,7 @@ int copy_csr_from(Topology* p, int pdev, Topology* o, int odev) {
     p->adjkPlain = o->adjkPlain;
     p->adjkFlagged = o->adjkFlagged;
     p->adjkResorted = o->adjkResorted;
+    p->adjkLeaf = o->adjkLeaf;
     p->adjkTargets = o->adjkTargets;
     p->csrUploaded = true;
     return 0;
@@ -3200,8 +3262,9 @@ void release_prepared(Topology* top) {
     top->kpBig = -1;
     top->hsegRows = top->hsegN = top->hmultiN = 0;
     top->csrUploaded = top->rowsSorted = false;
-    top->adjkPlain = top->adjkFlagged = top->adjkResorted = false;
+    top->adjkPlain = top->adjkFlagged = top->adjkResorted = top->adjkLeaf = false;
     top->adjkTargets.clear();
+    top->leafFor.clear();  // the records hold relabelled ids of the released preparation
     top->ordUploaded = false;
     top->ordHp = nullptr;
     top->hp.reset();
@@ -3414,6 +3477,7 @@ int shdtopo_set_option(Topology* top, const char* key, double value) {
     else if (k == "target_skip") top->targetSkip = value != 0;
     else if (k == "target_kappa") top->targetKappa = (int)value;
     else if (k == "target_resort") top->targetResort = value != 0;
+    else if (k == "leaf_targets") top->leafTargets = value != 0;
     else if (k == "exchange") {
         const int m = (int)value;
         if (m < 0 || m > 2) return -1;
@@ -4268,7 +4332,9 @@ int prepare_batch_path(Topology* top, const std::vector<uint32_t>& tgt, bool for
     const bool dense = top->tieReplay && (top->tieDenseOpt == 1 ||
                                           (top->tieDenseOpt < 0 && top->tieDense));
     if (top->replayAll || top->hasMultiEdges || dense) return 0;
-    const bool copyOk = top->adjkPlain ? !top->targetSkip : top->adjkTargets == tgt;
+    const bool leaf = leaf_targets_on(top);
+    const bool copyOk = top->adjkPlain ? !top->targetSkip
+                                       : top->adjkTargets == tgt && top->adjkLeaf == leaf;
     if (!copyOk || !top->d_adjk.p || !top->d_adj.p) return 0;
     const int K = batch_k(top);
     const size_t hparN = (size_t)std::min<int64_t>(top->parHubs, 1 << 20) * K;
@@ -4304,6 +4370,11 @@ int prepare_batch_path(Topology* top, const std::vector<uint32_t>& tgt, bool for
     HIPCHK(R.d_bst.ensure(ST_COUNT));
     HIPCHK(hipMemcpy(R.d_tgt.p, tgt.data(), 4 * (size_t)A, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(R.d_srcsh.p, sh.data(), 8 * (size_t)R.nsrc, hipMemcpyHostToDevice));
+    if (leaf) {  // the build's leaf-target records: the keep launch resolves the same targets so
+        const int r = ensure_leaf_targets(top, tgt, R.d_tgt.p, top->stream);
+        if (r) return r;
+        R.bws.tleaf = top->d_tleaf.p;
+    }
     R.batchOk = true;
     return 0;
 }

@@ -122,7 +122,9 @@ struct DevCSR {
     const double* selfLoss = nullptr;
     int rows_sorted = 0;  // adjacency rows ascending by neighbour (enables binary row search)
     // bit 30 of adjk's column word marks an attached vertex (a table target); the batch
-    // relaxation then skips pairs into non-target tail vertices that would expand nothing
+    // relaxation then skips pairs into non-target tail vertices that would expand nothing.
+    // 2: the marks are the effective target set's (leaf targets peeled, SlotWs::tleaf) and a
+    // record whose kappa field is +inf leads to a dead vertex: its pairs are dropped outright
     int tflags = 0;
     // (last: the undirected kernel's argument layout stays that of the fields above)
     int directed = 0;
@@ -166,7 +168,13 @@ struct SlotWs {
     // bstart[b + 1]) (at most K), nbat batches; nullptr = batch b takes [b kf, b kf + kf)
     const uint32_t* bstart = nullptr;
     int nbat = 0;
+    // leaf-target records (option "leaf_targets", launch_leaf_targets), 32 B per target k:
+    // {targets[k], uplink u (kNoLeaf: not peeled), f64 w} {f64 loss of the edge (u, t), 0, 0}.  A
+    // peeled target is resolved from its uplink: d(t) = fl(d(u) + w), parent(t) = u.  nullptr: no
+    // target is peeled (the kernel reads targets[k] alone)
+    const uint4* tleaf = nullptr;
 };
+constexpr uint32_t kNoLeaf = 0xFFFFFFFFu;
 constexpr int kBTraceWords = 12;  // u64 words per batch of SlotWs::btrace (per-batch trace / costs)
 
 // Incidence-order CSR of the heap replay (topo_replay.hip), relabelled vertex ids: row x holds
@@ -254,10 +262,20 @@ hipError_t launch_mark_targets(uint32_t* adjk, int64_t nadj, const uint32_t* tbi
 // := K(column).  part: scratch of hs.nseg doubles (the per-segment minima of cut rows)
 hipError_t launch_kfix_kap(const uint32_t* adj, const double* pot, int64_t nadj, double* kap,
                            hipStream_t stream);
+// dead (nullable): bitmap of the peeled leaf targets, whose K and Kt are forced to +inf (the edge
+// into one sorts past every kappa cut and the pair skip drops it)
 hipError_t launch_kfix_step(const uint32_t* rowptr, const uint32_t* adj, const double* kap_e,
                             const uint32_t* tbits, const double* Kin, double* Kout, int64_t V,
                             const HubSegs& hs, double* part, unsigned int* changed,
-                            hipStream_t stream);
+                            hipStream_t stream, const uint32_t* dead = nullptr);
+// Leaf targets of an undirected simple topology (rows without self loops): target k is peeled
+// when its row has exactly one entry (u, w) and u's row has more than one (of two mutually
+// pendant vertices neither is peeled).  Writes the SlotWs::tleaf record of every target, turns
+// tbits (in: the targets' bitmap) into the effective target set (targets - peeled) + {uplinks of
+// peeled}, sets the peeled vertices in dead (in: zero) and adds their number to *count.
+hipError_t launch_leaf_targets(const uint32_t* rowptr, const uint32_t* adj, const double* aloss,
+                               const uint32_t* targets, int A, uint4* tleaf, uint32_t* tbits,
+                               uint32_t* dead, uint32_t* count, hipStream_t stream);
 hipError_t launch_kfix_store(uint32_t* adjk, int64_t nadj, const double* K, hipStream_t stream);
 // re-sort every row of the relaxation copy (records, kappa array, probes, kappa0) by the
 // target-aware key kap' of the current target set (tbits) and K.  Scratch (KprimeScratch, sized

@@ -647,6 +647,14 @@ __device__ __forceinline__ void relax_batch_t(const uint32_t* Q, uint32_t nq, co
                 const bool skippable = kKapInRec && g.tflags &&
                                        (an[a] & 0x3FFFFFFFu) >= D.H && !((an[a] >> 30) & 1u);
                 const float kz0 = rec_kap0(apb[a]);
+                // a peeled leaf target (tflags 2: its field is +inf) is resolved from its uplink
+                // and needs no distance for any source: dropped outright -- kappa_useful alone
+                // keeps every pair while d_j(h0) is still +inf.  (Exactness never depends on it: a
+                // line the vertex does get is touched, reset and never read.)
+                if (skippable && g.tflags == 2 && kz0 == INFINITY) {
+                    mk = 0u;
+                    amk[a] = 0u;
+                }
                 while (mk) {
                     const uint32_t jj = (uint32_t)__ffs(mk) - 1u;
                     mk &= mk - 1u;
@@ -1201,8 +1209,21 @@ sssp_batch_kernel(DevCSR g, SlotWs ws, const uint32_t* __restrict__ sources,
                 for (uint32_t i = b + lane; i < b + c; i += 64) {
                     const uint32_t jj = i % nkv;  // target-major: a target's sources adjacent
                     const uint32_t k = i / nkv;
-                    rl_count(L, RL_EPI, true, targets + k);
-                    const uint32_t t = targets[k];
+                    // the target, or its leaf record {t, uplink, w} {loss} (one 32-B read)
+                    uint32_t t, lu = kNoLeaf;
+                    double lw = 0.0, ll = 0.0;
+                    if (ws.tleaf) {
+                        rl_count(L, RL_EPI, true, ws.tleaf + 2 * (size_t)k);
+                        const uint4 la = ws.tleaf[2 * (size_t)k];
+                        const uint2 lb = *reinterpret_cast<const uint2*>(ws.tleaf + 2 * (size_t)k + 1);
+                        t = la.x;
+                        lu = la.y;
+                        lw = __hiloint2double((int)la.w, (int)la.z);
+                        ll = __hiloint2double((int)lb.y, (int)lb.x);
+                    } else {
+                        rl_count(L, RL_EPI, true, targets + k);
+                        t = targets[k];
+                    }
                     const uint32_t src = L.src[jj];
                     double lat, rel;
                     uint32_t hcnt = 0;
@@ -1221,11 +1242,28 @@ sssp_batch_kernel(DevCSR g, SlotWs ws, const uint32_t* __restrict__ sources,
                             hcnt = 1;
                         }
                     } else {
-                        rl_count(L, RL_EPI, true, distO + (size_t)t * K + jj);
+                        // A peeled leaf target: d(t) = fl(d(u) + w) from its uplink's final distance
+                        // (hub rows are in the [V][K] block by now), its chain the uplink's with
+                        // the edge (u, t) at level 0 of the path buffer, so (1 - loss(u, t)) is
+                        // the forward product's last factor as ever.
+                        const bool leaf = lu != kNoLeaf;
+                        const uint32_t v0 = leaf ? lu : t;
+                        rl_count(L, RL_EPI, true, distO + (size_t)v0 * K + jj);
                         rl_count(L, RL_EPI, true, g.vloss + t);
-                        lat = bits2d(ld_l2_u64(&distO[(size_t)t * K + jj]));
+                        lat = bits2d(ld_l2_u64(&distO[(size_t)v0 * K + jj]));
                         bool amb = false, bad = false;
-                        uint32_t v = t;
+                        uint32_t v = v0;
+                        if (leaf) {
+                            lat = __dadd_rn(lat, lw);
+                            *pb_at(0u) = ll;
+                            hcnt = 1;
+                            if (KEEP) {  // the route walks start at the target's own record
+                                const unsigned long long lb = d2bits(ll);
+                                wl_count(L, WL_PREC, true, precO + (size_t)t * K + jj);
+                                precO[(size_t)t * K + jj] =
+                                    make_uint4(lu, eptv, (uint32_t)lb, (uint32_t)(lb >> 32));
+                            }
+                        }
                         while (v != src) {
                             // the pair record, L1-bypassing (written by other waves / workgroups)
                             typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -1255,8 +1293,12 @@ sssp_batch_kernel(DevCSR g, SlotWs ws, const uint32_t* __restrict__ sources,
                         } else {
                             atomicAdd(&stats[ST_LONGPATH], 1ull);
                             for (int x = (int)hcnt - 1; x >= 0; --x) {  // edge at depth x from t
-                                uint32_t y = t;
-                                for (int z = 0; z < x; ++z) y = precO[(size_t)y * K + jj].x & 0x3FFFFFFFu;
+                                if (leaf && x == 0) {  // the leaf edge: depth z >= 1 is z - 1 from u
+                                    rel *= (1.0 - ll);
+                                    continue;
+                                }
+                                uint32_t y = v0;
+                                for (int z = leaf ? 1 : 0; z < x; ++z) y = precO[(size_t)y * K + jj].x & 0x3FFFFFFFu;
                                 const uint4 r = precO[(size_t)y * K + jj];
                                 rel *= (1.0 - __hiloint2double((int)r.w, (int)r.z));
                             }
@@ -1685,10 +1727,19 @@ sssp_batch_kernel(DevCSR g, SlotWs ws, const uint32_t* __restrict__ sources,
         // takes its next start pair when its whole group is idle).
         for (uint32_t i = tid; i < (uint32_t)A * K; i += kSsspBlock) {
             const uint32_t j = i % K;
-            const uint32_t t = targets[i / K];
-            const bool p = j < (uint32_t)nk && t != L.src[j];
+            // a peeled leaf target's chain starts at its uplink (targets sharing one produce
+            // duplicate starts: the claims take them); none when the uplink is the source
+            uint32_t t, s;
+            if (ws.tleaf) {
+                const uint4 lr = ws.tleaf[2 * (size_t)(i / K)];
+                t = lr.x;
+                s = lr.y != kNoLeaf ? lr.y : t;
+            } else {
+                t = s = targets[i / K];
+            }
+            const bool p = j < (uint32_t)nk && t != L.src[j] && s != L.src[j];
             wl_count(L, WL_QUEUE, true, pcur + i);
-            pcur[i] = p ? t * K + j : kNoPair;
+            pcur[i] = p ? s * K + j : kNoPair;
         }
         uint32_t nF = (uint32_t)A * K;
         uint32_t wkind = kJobWalkSync;
@@ -2161,6 +2212,50 @@ hipError_t launch_mark_targets(uint32_t* adjk, int64_t nadj, const uint32_t* tbi
     return hipGetLastError();
 }
 
+// Leaf targets: a target t whose row holds one entry (u, w) -- self loops are not
+// in the rows and a multigraph never reaches the batch kernel, so one entry is one edge -- needs
+// no graph search: for every source but t itself d(t) = fl(d(u) + w), the one add the relaxation
+// u -> t performs at u's final distance, parent(t) = u without a tie, and t's chain is u's plus
+// the edge.  u's row must hold more than one entry: of two mutually pendant vertices neither is
+// peeled, and so a peeled vertex is never the uplink of another (its single neighbour has one
+// entry), which keeps the bitmap updates below free of conflicts.
+__global__ void leaf_targets_kernel(const uint32_t* __restrict__ rowptr,
+                                    const uint32_t* __restrict__ adj,
+                                    const double* __restrict__ aloss,
+                                    const uint32_t* __restrict__ targets, int A,
+                                    uint4* __restrict__ tleaf, uint32_t* __restrict__ tbits,
+                                    uint32_t* __restrict__ dead, uint32_t* __restrict__ count) {
+    const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (k >= A) return;
+    const uint32_t t = targets[k];
+    const uint32_t r0 = rowptr[t], r1 = rowptr[t + 1];
+    uint4 a = make_uint4(t, kNoLeaf, 0u, 0u), b = make_uint4(0u, 0u, 0u, 0u);
+    if (r1 - r0 == 1u) {
+        const AdjRec r = *reinterpret_cast<const AdjRec*>(adj + kAdjWords * r0);
+        const uint32_t u = r.a;
+        if (u != t && rowptr[u + 1] - rowptr[u] > 1u) {
+            const unsigned long long lb = d2bits(aloss[r0]);
+            a = make_uint4(t, u, r.b, r.c);
+            b = make_uint4((uint32_t)lb, (uint32_t)(lb >> 32), 0u, 0u);
+            atomicAnd(&tbits[t >> 5], ~(1u << (t & 31u)));
+            atomicOr(&tbits[u >> 5], 1u << (u & 31u));
+            atomicOr(&dead[t >> 5], 1u << (t & 31u));
+            atomicAdd(count, 1u);
+        }
+    }
+    tleaf[2 * (size_t)k] = a;
+    tleaf[2 * (size_t)k + 1] = b;
+}
+
+hipError_t launch_leaf_targets(const uint32_t* rowptr, const uint32_t* adj, const double* aloss,
+                               const uint32_t* targets, int A, uint4* tleaf, uint32_t* tbits,
+                               uint32_t* dead, uint32_t* count, hipStream_t stream) {
+    if (A <= 0) return hipSuccess;
+    hipLaunchKernelGGL(leaf_targets_kernel, dim3((unsigned)((A + 255) / 256)), dim3(256), 0, stream,
+                       rowptr, adj, aloss, targets, A, tleaf, tbits, dead, count);
+    return hipGetLastError();
+}
+
 // Target-aware kappa bound of every vertex (the relaxation's skip test, see phase B).  A pair
 // into a non-target tail vertex y is dropped when y's kappa field exceeds the landmark threshold at
 // the candidate; kappa0 (the row's smallest w - pi) says "y would relax nothing".  The fixpoint
@@ -2197,6 +2292,12 @@ __device__ __forceinline__ double kfix_term(const uint32_t* adj, const double* k
     return t;
 }
 
+// dead: the peeled leaf targets (launch_leaf_targets), K = Kt = +inf: a peeled vertex relaxes
+// nothing that reaches a target and is none of the effective set itself, so the edge into it takes
+// the key +inf in the re-sort and the field +inf in the records (the pair skip's explicit drop)
+__device__ __forceinline__ double kfix_dead(const uint32_t* dead, uint32_t x, double m) {
+    return dead && ((dead[x >> 5] >> (x & 31u)) & 1u) ? INFINITY : m;
+}
 __device__ __forceinline__ void kfix_put(double* Kout, double* Ktout, const uint32_t* tbits,
                                          uint32_t x, double m) {
     Kout[x] = m;
@@ -2213,7 +2314,8 @@ __global__ void kfix_step_kernel(const uint32_t* __restrict__ rowptr,
                                  const double* __restrict__ Kin, const double* __restrict__ Ktin,
                                  double* __restrict__ Kout, double* __restrict__ Ktout,
                                  int64_t V, HubSegs hs, double* __restrict__ part,
-                                 unsigned int* __restrict__ changed) {
+                                 unsigned int* __restrict__ changed,
+                                 const uint32_t* __restrict__ dead) {
     const uint32_t lane = threadIdx.x & 63u;
     const int64_t gt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t gs = (int64_t)gridDim.x * blockDim.x;
@@ -2234,6 +2336,7 @@ __global__ void kfix_step_kernel(const uint32_t* __restrict__ rowptr,
         }
         if (lane == 0) {
             if (sg.y == r0 && e == r1) {
+                m = kfix_dead(dead, x, m);
                 ch |= Kin && !(m == Kin[x]);
                 kfix_put(Kout, Ktout, tbits, x, m);
             } else {
@@ -2274,6 +2377,7 @@ __global__ void kfix_step_kernel(const uint32_t* __restrict__ rowptr,
             const double t = kfix_term(adj, kap_e, Ktin, k);
             m = t < m ? t : m;
         }
+        m = kfix_dead(dead, (uint32_t)x, m);
         ch |= Kin && !(m == Kin[x]);
         kfix_put(Kout, Ktout, tbits, (uint32_t)x, m);
     }
@@ -2284,7 +2388,8 @@ __global__ void kfix_step_kernel(const uint32_t* __restrict__ rowptr,
 __global__ void kfix_multi_kernel(const double* __restrict__ Kin, double* __restrict__ Kout,
                                   double* __restrict__ Ktout, const uint32_t* __restrict__ tbits,
                                   HubSegs hs, const double* __restrict__ part,
-                                  unsigned int* __restrict__ changed) {
+                                  unsigned int* __restrict__ changed,
+                                  const uint32_t* __restrict__ dead) {
     const uint32_t lane = threadIdx.x & 63u;
     const int64_t gt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t gs = (int64_t)gridDim.x * blockDim.x;
@@ -2302,6 +2407,7 @@ __global__ void kfix_multi_kernel(const double* __restrict__ Kin, double* __rest
             m = y < m ? y : m;
         }
         if (lane == 0) {
+            m = kfix_dead(dead, mr.x, m);
             ch |= Kin && !(m == Kin[mr.x]);
             kfix_put(Kout, Ktout, tbits, mr.x, m);
         }
@@ -2345,15 +2451,15 @@ hipError_t launch_kfix_kap(const uint32_t* adj, const double* pot, int64_t nadj,
 hipError_t launch_kfix_step(const uint32_t* rowptr, const uint32_t* adj, const double* kap_e,
                             const uint32_t* tbits, const double* Kin, double* Kout, int64_t V,
                             const HubSegs& hs, double* part, unsigned int* changed,
-                            hipStream_t stream) {
+                            hipStream_t stream, const uint32_t* dead) {
     if (V <= 0) return hipSuccess;
     const int64_t g = std::min<int64_t>(std::max<int64_t>((V + 255) / 256, (hs.nseg + 3) / 4), 256 * 32);
     const double* Ktin = Kin ? Kin + V : nullptr;
     hipLaunchKernelGGL(kfix_step_kernel, dim3((unsigned)g), dim3(256), 0, stream, rowptr, adj,
-                       kap_e, tbits, Kin, Ktin, Kout, Kout + V, V, hs, part, changed);
+                       kap_e, tbits, Kin, Ktin, Kout, Kout + V, V, hs, part, changed, dead);
     if (hs.nmulti > 0)
         hipLaunchKernelGGL(kfix_multi_kernel, dim3((hs.nmulti + 3) / 4), dim3(256), 0, stream, Kin,
-                           Kout, Kout + V, tbits, hs, part, changed);
+                           Kout, Kout + V, tbits, hs, part, changed, dead);
     return hipGetLastError();
 }
 
