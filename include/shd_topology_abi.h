@@ -555,6 +555,89 @@ int64_t shdtopo_link_load(Topology* top, const uint32_t* srcIP, const uint32_t* 
                           uint64_t* vertexLoad /* u64[V], may be NULL */);
 int shdtopo_link_load_stats(Topology* top, ShdLoadStats* out);
 
+/* ---- link crossings: which flows cross a set of watched links and routers ----
+ * Link load's inverse question -- "which of my flows go over this link or through this router":
+ * the blast radius of a link before it is failed, the circuits that share a bottleneck.  For n
+ * flows (source host, destination host, weight; IPs in network order, duplicates and any order are
+ * fine), ne watched edges (edge ids, document order) and nv watched vertices (original vertex ids)
+ * the call reports every hop of a flow's route that goes over a watched edge or arrives at a
+ * watched vertex, without writing a single route out.
+ *
+ * Flow i's route is exactly the route shdtopo_trace_routes reports for (srcIP[i], dstIP[i]): the
+ * forward route of the source's row for the current attached set, each hop over the igraph_get_eid
+ * edge (the lowest id of a parallel group -- watching a higher id of the group reports nothing),
+ * the self loop (hop 0) for two hosts on one vertex or src == dst.  For the hop number `hop` from
+ * vertex a = vertices[hop] to b = vertices[hop + 1] over edge e:
+ *   e == watchEdge[k]    one record {i, k, hop, reverse}: either direction counts, reverse = 1 when
+ *                        a != eu[e] (link load's reverse half; 0 for every self loop and every arc
+ *                        of a directed topology);
+ *   b == watchVertex[k]  one record {i, ne + k, hop, 0}: link load's vertexLoad rule -- every
+ *                        vertex of the route but its first; a self pair arrives once, over its loop.
+ * A hop with both yields two records, the edge record first.  Records are ordered by flow
+ * ascending, then hop ascending, then edge before vertex; flowOffset[i] (i64[n + 1], may be NULL)
+ * is the running sum of the flows' record counts and flowOffset[n] the return value, the total
+ * number of crossings.  The bytes of out do not depend on chunking, scheduling, "trace_batch" or
+ * which chain source served a flow.  A call with cap = 0 (out may then be NULL) sizes the buffer.
+ * With a cap that is too small flow i's records are written iff flowOffset[i + 1] <= cap and
+ * nothing at or beyond cap is touched; flowOffset, watchCount, watchWeight and the return value
+ * are complete regardless.
+ *
+ * watchCount[k] (u64[ne + nv], may be NULL) is the number of records of watch k, watchWeight[k]
+ * (the same) the sum of their flows' weights (weight = NULL: 1 each), unsigned 64-bit and
+ * wrapping: for an edge watch edgeLoad[e] + edgeLoad[E + e] of shdtopo_link_load on the same
+ * flows, for a vertex watch vertexLoad[v].  Requests with an unattached end, and unroutable ones
+ * (a broken chain, a self pair without a self loop), contribute nothing and are counted in the
+ * statistics.  ne + nv == 0 is valid: the call returns 0 and every offset is 0 (on an SSSP topology
+ * nothing is walked then: routed and broken stay 0).
+ *
+ * Returns a negative value on an error; -1: bad arguments -- NULL top; n, ne, nv or cap negative;
+ * a NULL IP array with n > 0; a NULL watch array with a positive count; cap > 0 with NULL out; an
+ * edge id outside [0, E) or a vertex id outside [0, V); a duplicate id within one watch list.
+ *
+ * SSSP topologies: the distinct sources are taken in chunks (option "trace_chunk") and get their
+ * chains as in a trace: from the batch kernel's parent records where that is exact (option
+ * "trace_batch"), else from the exact heap replay; option "load_walk" has no meaning here.  The
+ * walks themselves are microseconds to milliseconds.  Complete topologies are
+ * answered on the host from the parsed graph (one hop over the direct edge): no device is used.
+ * A multi-device topology runs on its first device.  Like a trace and a load, the call holds the
+ * build lock, materialises no lazy row, pushes no minimum, neither invalidates nor rebuilds the
+ * table and leaves ShdStats, the trace statistics and the load statistics as they were. */
+typedef struct {
+    int32_t flow;     /* request index i */
+    int32_t watch;    /* k in [0, ne): watchEdge[k];  ne + k: watchVertex[k] */
+    int32_t hop;      /* 0-based hop from the source: the hop vertices[hop] -> vertices[hop + 1]
+                         of the route shdtopo_trace_routes reports for the flow */
+    int32_t reverse;  /* edge watch: 1 when the hop does not leave eu[e] (link load's reverse
+                         half); 0 for self loops, directed arcs and every vertex watch */
+} ShdCrossing;
+typedef struct {
+    double  total_ms;        /* wall time of the call */
+    double  replay_ms;       /* event time of its heap-replay launches only */
+    double  kernel_ms;       /* event time of everything but the replay and the keep launches */
+    double  ids_ms;          /* edge-id upload, first trace/load/crossings of a topology, else 0 */
+    int64_t requests;        /* n */
+    int64_t routed;          /* requests whose route was walked */
+    int64_t unattached;      /* requests with an unattached end (contribute nothing) */
+    int64_t broken;          /* unroutable / broken chain / self pair without a self loop */
+    int64_t sources;         /* distinct source vertices of the call, either path */
+    int64_t chunks;          /* source chunks */
+    int64_t crossings;       /* the call's return value */
+    int64_t flows_hit;       /* flows with at least one record */
+    double  batch_ms;        /* event time of the batch kernel's keep launches */
+    int64_t batch_sources;   /* distinct sources answered from the batch kernel's parent records */
+    int64_t batch_fallback;  /* sources that ran a keep launch and then went to the heap replay */
+} ShdCrossStats;
+
+int64_t shdtopo_link_crossings(Topology* top, const uint32_t* srcIP, const uint32_t* dstIP,
+                               const uint64_t* weight /* NULL: 1 each */, int64_t n,
+                               const int32_t* watchEdge, int64_t ne /* edge ids, document order */,
+                               const int32_t* watchVertex, int64_t nv /* original vertex ids */,
+                               int64_t* flowOffset /* i64[n + 1], may be NULL */,
+                               ShdCrossing* out, int64_t cap,
+                               uint64_t* watchCount, uint64_t* watchWeight
+                               /* u64[ne + nv] each, may be NULL */);
+int shdtopo_link_crossings_stats(Topology* top, ShdCrossStats* out);
+
 /* Test hook: the device graph preparation (topo_prep.hip) read back -- perm
  * int32[V] (relabelled -> original vertex), rowptr u32[V+1], the adjacency columns u32[2E']
  * (relabelled ids, rows ascending by neighbour), pi f64[V] (= d(h0, .), relabelled ids) and the

@@ -83,6 +83,17 @@ class ShdLoadStats(ctypes.Structure):
                 ("batch_ms", dbl), ("batch_sources", i64), ("batch_fallback", i64)]
 
 
+class ShdCrossing(ctypes.Structure):
+    _fields_ = [("flow", i32), ("watch", i32), ("hop", i32), ("reverse", i32)]
+
+
+class ShdCrossStats(ctypes.Structure):
+    _fields_ = [("total_ms", dbl), ("replay_ms", dbl), ("kernel_ms", dbl), ("ids_ms", dbl),
+                ("requests", i64), ("routed", i64), ("unattached", i64), ("broken", i64),
+                ("sources", i64), ("chunks", i64), ("crossings", i64), ("flows_hit", i64),
+                ("batch_ms", dbl), ("batch_sources", i64), ("batch_fallback", i64)]
+
+
 class ShdSynthParams(ctypes.Structure):
     _fields_ = [("seed", u64), ("n_routers", i64), ("n_poi", i64), ("n_edges", i64),
                 ("integer_latency", ctypes.c_int), ("alpha", dbl), ("directed", ctypes.c_int)]
@@ -139,6 +150,8 @@ SIGNATURES = {
     "shdtopo_trace_stats": (ctypes.c_int, [P, P]),
     "shdtopo_link_load": (i64, [P, P, P, P, i64, P, P]),
     "shdtopo_link_load_stats": (ctypes.c_int, [P, P]),
+    "shdtopo_link_crossings": (i64, [P, P, P, P, i64, P, i64, P, i64, P, P, i64, P, P]),
+    "shdtopo_link_crossings_stats": (ctypes.c_int, [P, P]),
     "shdtopo_test_segsort": (ctypes.c_int, [P, i64, P, i64, ctypes.c_int, P, P]),
     "shdtopo_test_batch_layout": (ctypes.c_int, [P, i64, dbl, ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_int, P, P, P]),

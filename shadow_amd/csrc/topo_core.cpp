@@ -469,6 +469,7 @@ struct _Topology {
     int loadWalk = 1;            // option "load_walk": 1 = the per-request walk (the default:
                                  // DESIGN.md 3.7), 0 = the leaf-to-root tree accumulation
     ShdLoadStats loadStats{};    // the last call's own counters
+    ShdCrossStats crossStats{};  // link crossings (shdtopo_link_crossings, topo_cross.hip)
 
     // multi-GPU build inside the library (one Shadow process): device d builds
     // rows [d*R, (d+1)*R) with its own stream / workspace (a peer Topology on that device),
@@ -4806,6 +4807,256 @@ int64_t load_replay(Topology* top, const std::vector<int32_t>& sv, const std::ve
     return ls->routed;
 }
 
+// ---------------------------------------------------------------------------------------------
+// link crossings (include/shd_topology_abi.h shdtopo_link_crossings; kernels in topo_cross.hip)
+// ---------------------------------------------------------------------------------------------
+static_assert(sizeof(ShdCrossing) == 16 && sizeof(CrossRec) == sizeof(ShdCrossing) &&
+                  offsetof(ShdCrossing, flow) == offsetof(CrossRec, flow) &&
+                  offsetof(ShdCrossing, watch) == offsetof(CrossRec, watch) &&
+                  offsetof(ShdCrossing, hop) == offsetof(CrossRec, hop) &&
+                  offsetof(ShdCrossing, reverse) == offsetof(CrossRec, reverse),
+              "CrossRec is the device image of ShdCrossing");
+
+// The watch set of one call: the ids of each list ascending with their watch index (edges k,
+// vertices ne + k; original vertex ids).  false: an id out of range or twice in its list.
+struct WatchSet {
+    std::vector<int32_t> eids, eidx, vids, vidx;
+    static bool sorted_ids(const int32_t* id, int64_t n, int64_t limit, int32_t idx0,
+                           std::vector<int32_t>& ids, std::vector<int32_t>& idx) {
+        std::vector<std::pair<int32_t, int32_t>> s((size_t)n);
+        for (int64_t k = 0; k < n; k++) {
+            if (id[k] < 0 || (int64_t)id[k] >= limit) return false;
+            s[(size_t)k] = {id[k], (int32_t)(idx0 + k)};
+        }
+        std::sort(s.begin(), s.end());
+        ids.resize((size_t)n);
+        idx.resize((size_t)n);
+        for (size_t k = 0; k < (size_t)n; k++) {
+            if (k > 0 && s[k].first == s[k - 1].first) return false;
+            ids[k] = s[k].first;
+            idx[k] = s[k].second;
+        }
+        return true;
+    }
+    bool init(const HostGraph& g, const int32_t* we, int64_t ne, const int32_t* wv, int64_t nv) {
+        return sorted_ids(we, ne, g.E, 0, eids, eidx) &&
+               sorted_ids(wv, nv, g.V, (int32_t)ne, vids, vidx);
+    }
+    static int32_t find(const std::vector<int32_t>& ids, const std::vector<int32_t>& idx,
+                        int32_t x) {
+        const auto it = std::lower_bound(ids.begin(), ids.end(), x);
+        return it != ids.end() && *it == x ? idx[(size_t)(it - ids.begin())] : -1;
+    }
+    int32_t edge(int32_t e) const { return find(eids, eidx, e); }
+    int32_t vertex(int32_t v) const { return find(vids, vidx, v); }
+};
+
+// Complete topologies, on the host as load_complete: one hop (hop 0) over the direct edge, a self
+// pair over the loop; the edge record before the vertex record.
+int64_t cross_complete(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
+                       const uint64_t* weight, int64_t n, const WatchSet& ws, int64_t* flowOffset,
+                       ShdCrossing* out, int64_t cap, uint64_t* watchCount, uint64_t* watchWeight,
+                       ShdCrossStats* cs) {
+    const HostGraph& g = top->g;
+    const std::vector<int32_t> pe = complete_pair_eids(top, sv, dv, n);
+    int64_t off = 0;
+    for (int64_t i = 0; i < n; i++) {
+        if (flowOffset) flowOffset[i] = off;
+        const int32_t s = sv[(size_t)i], d = dv[(size_t)i];
+        if (s < 0 || d < 0) continue;  // counted by the caller
+        const int32_t e = pe[(size_t)i];
+        if (e < 0) {
+            cs->broken++;
+            continue;
+        }
+        cs->routed++;
+        const uint64_t w = weight ? weight[i] : 1;
+        ShdCrossing rec[2];
+        int m = 0;
+        const int32_t ke = ws.edge(e), kv = ws.vertex(d);
+        if (ke >= 0) rec[m++] = ShdCrossing{(int32_t)i, ke, 0, s != g.eu[(size_t)e] ? 1 : 0};
+        if (kv >= 0) rec[m++] = ShdCrossing{(int32_t)i, kv, 0, 0};
+        for (int k = 0; k < m; k++) {
+            if (watchCount) watchCount[rec[k].watch]++;
+            if (watchWeight) watchWeight[rec[k].watch] += w;
+            if (off + m <= cap) out[off + k] = rec[k];
+        }
+        if (m > 0) cs->flows_hit++;
+        off += m;
+    }
+    if (flowOffset) flowOffset[n] = off;
+    return off;
+}
+
+// SSSP topologies: the distinct sources in chunks -- chains from the batch kernel's pair records
+// or the replay (chunk_chains), whatever "load_walk" says -- link load's validation, then the
+// count and write walks of topo_cross.hip; the records are staged per chunk and placed once the
+// last chunk is walked (the structure of trace_replay)
+int64_t cross_replay(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
+                     const uint64_t* weight, int64_t n, const WatchSet& wset, int64_t* flowOffset,
+                     ShdCrossing* out, int64_t cap, uint64_t* watchCount, uint64_t* watchWeight,
+                     ShdCrossStats* cs) {
+    ReplayReqs R;
+    int r = group_replay_requests(top, sv, dv, n, &cs->ids_ms, false, R);
+    if (r) return r;
+    hipStream_t st = top->stream;
+    const size_t nv = R.nv, mmax = R.mmax, V = (size_t)top->g.V, E = (size_t)top->g.E;
+    const size_t ne = wset.eids.size(), nvw = wset.vids.size(), nw = ne + nvw;
+    cs->sources = R.nsrc;
+
+    // the watch set: bits by edge id and by relabelled vertex, the sorted ids for the hits
+    std::vector<uint32_t> ebits(E / 32 + 1, 0u), vbits(V / 32 + 1, 0u);
+    for (int32_t e : wset.eids) ebits[(size_t)e >> 5] |= 1u << (e & 31);
+    std::vector<std::pair<int32_t, int32_t>> rv(nvw);
+    for (size_t k = 0; k < nvw; k++) {
+        const int32_t x = top->hp->inv[(size_t)wset.vids[k]];
+        vbits[(size_t)x >> 5] |= 1u << (x & 31);
+        rv[k] = {x, wset.vidx[k]};
+    }
+    std::sort(rv.begin(), rv.end());
+    std::vector<int32_t> vids(nvw), vidx(nvw);
+    for (size_t k = 0; k < nvw; k++) {
+        vids[k] = rv[k].first;
+        vidx[k] = rv[k].second;
+    }
+    DevBuf<uint32_t> d_ebits, d_vbits;
+    DevBuf<int32_t> d_eids, d_eidx, d_vids, d_vidx, d_hops;
+    DevBuf<unsigned long long> d_w, d_wcount, d_wweight, d_cnt, d_pcnt, d_ccnt;
+    DevBuf<int64_t> d_gcnt, d_goff, d_lcnt, d_coff, d_loff;
+    HIPCHK(d_ebits.ensure(ebits.size())); HIPCHK(d_vbits.ensure(vbits.size()));
+    HIPCHK(d_eids.ensure(std::max<size_t>(1, ne))); HIPCHK(d_eidx.ensure(std::max<size_t>(1, ne)));
+    HIPCHK(d_vids.ensure(std::max<size_t>(1, nvw))); HIPCHK(d_vidx.ensure(std::max<size_t>(1, nvw)));
+    HIPCHK(d_wcount.ensure(nw)); HIPCHK(d_wweight.ensure(nw));
+    HIPCHK(hipMemcpy(d_ebits.p, ebits.data(), 4 * ebits.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_vbits.p, vbits.data(), 4 * vbits.size(), hipMemcpyHostToDevice));
+    if (ne) {
+        HIPCHK(hipMemcpy(d_eids.p, wset.eids.data(), 4 * ne, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_eidx.p, wset.eidx.data(), 4 * ne, hipMemcpyHostToDevice));
+    }
+    if (nvw) {
+        HIPCHK(hipMemcpy(d_vids.p, vids.data(), 4 * nvw, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_vidx.p, vidx.data(), 4 * nvw, hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemsetAsync(d_wcount.p, 0, 8 * nw, st));
+    HIPCHK(hipMemsetAsync(d_wweight.p, 0, 8 * nw, st));
+    CrossWatch cw;
+    cw.ebits = d_ebits.p;
+    cw.vbits = d_vbits.p;
+    cw.eids = d_eids.p;
+    cw.eidx = d_eidx.p;
+    cw.vids = d_vids.p;
+    cw.vidx = d_vidx.p;
+    cw.ne = (int32_t)ne;
+    cw.nv = (int32_t)nvw;
+    cw.E = (int64_t)E;
+    cw.eu = top->d_eu.p;
+    cw.wcount = d_wcount.p;
+    cw.wweight = d_wweight.p;
+
+    std::vector<unsigned long long> rw(nv, 1ull);
+    if (weight)
+        for (size_t q = 0; q < nv; q++) rw[q] = weight[R.order[q]];
+    HIPCHK(d_w.ensure(nv));
+    HIPCHK(d_hops.ensure(nv));
+    HIPCHK(d_cnt.ensure(LD_COUNT)); HIPCHK(d_pcnt.ensure(LD_COUNT)); HIPCHK(d_ccnt.ensure(CR_COUNT));
+    HIPCHK(d_gcnt.ensure((size_t)n + 1)); HIPCHK(d_goff.ensure((size_t)n + 1));
+    HIPCHK(d_lcnt.ensure(mmax + 1)); HIPCHK(d_coff.ensure(mmax + 1)); HIPCHK(d_loff.ensure(nv));
+    HIPCHK(hipMemcpy(d_w.p, rw.data(), 8 * nv, hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(d_cnt.p, 0, 8 * LD_COUNT, st));
+    HIPCHK(hipMemsetAsync(d_ccnt.p, 0, 8 * CR_COUNT, st));
+    // requests with an unattached end have no records; the count pass writes the others
+    HIPCHK(hipMemsetAsync(d_gcnt.p, 0, 8 * ((size_t)n + 1), st));
+
+    std::vector<std::unique_ptr<DevBuf<CrossRec>>> stage;  // per chunk
+    float ms = 0;
+    unsigned long long pcnt[LD_COUNT] = {};  // the pair walks' validation, as load_replay
+    for (int s0 = 0; s0 < R.nsrc; s0 += R.chunk) {
+        const int s1 = std::min(R.nsrc, s0 + R.chunk);
+        TraceReqs rq = R.reqs(s0, s1);
+        const size_t q0 = R.srcStart[(size_t)s0], m = (size_t)rq.n;
+        HIPCHK(hipMemsetAsync(d_lcnt.p, 0, 8 * (m + 1), st));
+        r = chunk_chains(top, R, s0, s1, &rq,
+                         [&](const TraceReqs& q, bool) {
+                             HIPCHK(hipMemsetAsync(d_pcnt.p, 0, 8 * LD_COUNT, st));
+                             HIPCHK(launch_load_validate_pairs(R.csr, R.pc, q, d_w.p + q0,
+                                                               d_hops.p + q0, d_pcnt.p,
+                                                               R.d_broken.p, st));
+                             return 0;
+                         },
+                         &cs->batch_ms, &cs->batch_sources, &cs->batch_fallback);
+        if (r) return r;
+        // both chain sources write the same counts and staging: each takes its requests
+        const bool pairs = R.mixed && R.nfall < s1 - s0;
+        unsigned long long c[LD_COUNT] = {};
+        if (pairs) {
+            HIPCHK(hipMemcpyAsync(c, d_pcnt.p, 8 * LD_COUNT, hipMemcpyDeviceToHost, st));
+            HIPCHK(launch_cross_count_pairs(R.csr, R.pc, R.ids, rq, d_w.p + q0, d_hops.p + q0, cw,
+                                            d_lcnt.p, d_gcnt.p, d_ccnt.p, st));
+        }
+        if (R.nfall > 0) {
+            HIPCHK(launch_load_validate(R.csr, R.ws, rq, d_w.p + q0, d_hops.p + q0, d_cnt.p, st));
+            HIPCHK(launch_cross_count(R.csr, R.ws, R.ids, rq, d_w.p + q0, d_hops.p + q0, cw,
+                                      d_lcnt.p, d_gcnt.p, d_ccnt.p, st));
+        }
+        HIPCHK(trace_exclusive_scan(d_lcnt.p, d_coff.p, (int64_t)m + 1, st));
+        int64_t tot = 0;
+        HIPCHK(hipMemcpy(&tot, d_coff.p + m, 8, hipMemcpyDeviceToHost));
+        stage.emplace_back(new DevBuf<CrossRec>());
+        DevBuf<CrossRec>& stg = *stage.back();
+        HIPCHK(stg.ensure((size_t)std::max<int64_t>(1, tot)));
+        if (pairs && tot > 0)
+            HIPCHK(launch_cross_write_pairs(R.csr, R.pc, R.ids, rq, d_hops.p + q0, cw, d_coff.p,
+                                            stg.p, st));
+        if (R.nfall > 0 && tot > 0)
+            HIPCHK(launch_cross_write(R.csr, R.ws, R.ids, rq, d_hops.p + q0, cw, d_coff.p, stg.p, st));
+        HIPCHK(hipMemcpyAsync(d_loff.p + q0, d_coff.p, 8 * m, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipEventRecord(R.ev.e[2], st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int i = 0; i < LD_COUNT; i++) pcnt[i] += c[i];
+        r = chunk_times(R, &cs->replay_ms, &cs->kernel_ms);
+        if (r) return r;
+        cs->chunks++;
+    }
+
+    // the call's offsets: exclusive scan in request order, then the flows that fit are copied out
+    HIPCHK(hipEventRecord(R.ev.e[0], st));
+    HIPCHK(trace_exclusive_scan(d_gcnt.p, d_goff.p, n + 1, st));
+    std::vector<int64_t> goff((size_t)n + 1);
+    HIPCHK(hipMemcpy(goff.data(), d_goff.p, 8 * ((size_t)n + 1), hipMemcpyDeviceToHost));
+    const int64_t total = goff[(size_t)n];
+    // offsets ascend: the flows written are those ending at or below cap, and fill [0, fit)
+    const int64_t fit =
+        *(std::upper_bound(goff.begin(), goff.end(), std::min(cap, total)) - 1);
+    DevBuf<CrossRec> d_out;
+    if (fit > 0) {
+        HIPCHK(d_out.ensure((size_t)fit));
+        size_t c = 0;
+        for (int s0 = 0; s0 < R.nsrc; s0 += R.chunk, c++)
+            HIPCHK(launch_cross_scatter(R.reqs(s0, std::min(R.nsrc, s0 + R.chunk)), d_goff.p,
+                                        d_loff.p + R.srcStart[(size_t)s0], stage[c]->p, d_out.p,
+                                        fit, st));
+    }
+    HIPCHK(hipEventRecord(R.ev.e[1], st));
+    unsigned long long cnt[LD_COUNT] = {}, ccnt[CR_COUNT] = {};
+    HIPCHK(hipMemcpyAsync(cnt, d_cnt.p, 8 * LD_COUNT, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(ccnt, d_ccnt.p, 8 * CR_COUNT, hipMemcpyDeviceToHost, st));
+    if (fit > 0)
+        HIPCHK(hipMemcpyAsync(out, d_out.p, sizeof(ShdCrossing) * (size_t)fit, hipMemcpyDeviceToHost, st));
+    if (watchCount && nw)
+        HIPCHK(hipMemcpyAsync(watchCount, d_wcount.p, 8 * nw, hipMemcpyDeviceToHost, st));
+    if (watchWeight && nw)
+        HIPCHK(hipMemcpyAsync(watchWeight, d_wweight.p, 8 * nw, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipEventElapsedTime(&ms, R.ev.e[0], R.ev.e[1]));
+    cs->kernel_ms += ms;
+    if (flowOffset) std::copy(goff.begin(), goff.end(), flowOffset);
+    cs->routed = (int64_t)(cnt[LD_ROUTED] + pcnt[LD_ROUTED]);
+    cs->broken = (int64_t)(cnt[LD_BROKEN] + pcnt[LD_BROKEN]);
+    cs->flows_hit = (int64_t)ccnt[CR_FLOWS];
+    if ((int64_t)ccnt[CR_RECORDS] != total) return -3;
+    return total;
+}
+
 }  // namespace
 
 extern "C" {
@@ -4889,6 +5140,58 @@ int shdtopo_link_load_stats(Topology* top, ShdLoadStats* out) {
     if (!top || !out) return -1;
     std::lock_guard<std::mutex> lk(top->buildMu);
     *out = top->loadStats;
+    return 0;
+}
+
+int64_t shdtopo_link_crossings(Topology* top, const uint32_t* srcIP, const uint32_t* dstIP,
+                               const uint64_t* weight, int64_t n, const int32_t* watchEdge,
+                               int64_t ne, const int32_t* watchVertex, int64_t nv,
+                               int64_t* flowOffset, ShdCrossing* out, int64_t cap,
+                               uint64_t* watchCount, uint64_t* watchWeight) {
+    if (!top || n < 0 || n > 0x7FFFFFFE || ne < 0 || nv < 0 || cap < 0) return -1;
+    if (n > 0 && (!srcIP || !dstIP)) return -1;
+    if ((ne > 0 && !watchEdge) || (nv > 0 && !watchVertex) || (cap > 0 && !out)) return -1;
+    if (ne > top->g.E || nv > top->g.V) return -1;  // (more ids than there are: a duplicate)
+    const auto t0 = std::chrono::steady_clock::now();
+    std::lock_guard<std::mutex> lk(top->buildMu);
+    WatchSet ws;
+    if (!ws.init(top->g, watchEdge, ne, watchVertex, nv)) return -1;
+    ShdCrossStats cs{};
+    cs.requests = n;
+    compute_geometry(top);
+    // the outputs are overwritten, not accumulated into
+    if (flowOffset) std::fill(flowOffset, flowOffset + (size_t)n + 1, (int64_t)0);
+    if (watchCount) std::fill(watchCount, watchCount + (size_t)(ne + nv), (uint64_t)0);
+    if (watchWeight) std::fill(watchWeight, watchWeight + (size_t)(ne + nv), (uint64_t)0);
+    // both ends on a vertex of the current attached set, as a trace
+    std::vector<int32_t> sv((size_t)n), dv((size_t)n);
+    int64_t nvalid = 0;
+    for (int64_t i = 0; i < n; i++) {
+        int32_t s = vertex_of_ip(top, srcIP[i]), d = vertex_of_ip(top, dstIP[i]);
+        if (s >= 0 && (s >= top->g.V || top->colOf[(size_t)s] < 0)) s = -1;
+        if (d >= 0 && (d >= top->g.V || top->colOf[(size_t)d] < 0)) d = -1;
+        sv[(size_t)i] = s;
+        dv[(size_t)i] = d;
+        if (s >= 0 && d >= 0) nvalid++;
+    }
+    cs.unattached = n - nvalid;
+    int64_t total = 0;
+    if (top->isComplete)
+        total = cross_complete(top, sv, dv, weight, n, ws, flowOffset, out, cap, watchCount,
+                               watchWeight, &cs);
+    else if (nvalid > 0 && ne + nv > 0)  // an empty watch set: nothing to walk for
+        total = cross_replay(top, sv, dv, weight, n, ws, flowOffset, out, cap, watchCount,
+                             watchWeight, &cs);
+    cs.crossings = total < 0 ? 0 : total;
+    cs.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    top->crossStats = cs;
+    return total;
+}
+
+int shdtopo_link_crossings_stats(Topology* top, ShdCrossStats* out) {
+    if (!top || !out) return -1;
+    std::lock_guard<std::mutex> lk(top->buildMu);
+    *out = top->crossStats;
     return 0;
 }
 

@@ -476,6 +476,58 @@ hipError_t launch_load_push(const ReplayCSR& g, const ReplayWs& ws, const TraceI
 hipError_t launch_load_permute(int64_t V, const int32_t* perm, const unsigned long long* vload,
                                unsigned long long* out, hipStream_t stream);
 
+// ---- link crossings (topo_cross.hip): the flows that cross a set of watched edges / vertices ----
+// one crossing: the device image of ShdCrossing (include/shd_topology_abi.h)
+struct __attribute__((aligned(16))) CrossRec {
+    int32_t flow, watch, hop, reverse;
+};
+// The watch set of one call: one bit per edge id and per relabelled vertex for the per-hop test;
+// on a hit the sorted ids (edges: edge ids; vertices: relabelled ids) are searched for the watch
+// index (edges k, vertices ne + k).  wcount / wweight u64[ne + nv]: records and summed flow weight
+// of every watch.
+struct CrossWatch {
+    const uint32_t* ebits = nullptr;
+    const uint32_t* vbits = nullptr;
+    const int32_t* eids = nullptr;   // ne, ascending
+    const int32_t* eidx = nullptr;
+    const int32_t* vids = nullptr;   // nv, ascending
+    const int32_t* vidx = nullptr;
+    int32_t ne = 0, nv = 0;
+    int64_t E = 0;
+    const int32_t* eu = nullptr;     // parsed edge tails, original ids
+    unsigned long long* wcount = nullptr;
+    unsigned long long* wweight = nullptr;
+};
+// counters of one call (u64 words, zeroed by the caller)
+enum { CR_RECORDS = 0, CR_FLOWS, CR_COUNT };
+// Count: request q (hops[q] from launch_load_validate[_pairs], < 1: no records) walks rdst -> rsrc
+// and tests every hop's edge and arrival vertex; its record count into lcnt[q] (chunk order) and
+// gcnt[ridx] (request order), the watches' totals into cw.wcount / cw.wweight, the records and the
+// flows with one into cnt[CR_RECORDS / CR_FLOWS].
+hipError_t launch_cross_count(const ReplayCSR& g, const ReplayWs& ws, const TraceIds& ids,
+                              const TraceReqs& rq, const unsigned long long* w,
+                              const int32_t* hops, const CrossWatch& cw, int64_t* lcnt,
+                              int64_t* gcnt, unsigned long long* cnt, hipStream_t stream);
+// Write: the same walk fills the request's segment [loff[q], loff[q + 1]) of the chunk's staging
+// array from its end backwards: route order, within a hop the edge record before the vertex's.
+hipError_t launch_cross_write(const ReplayCSR& g, const ReplayWs& ws, const TraceIds& ids,
+                              const TraceReqs& rq, const int32_t* hops, const CrossWatch& cw,
+                              const int64_t* loff, CrossRec* stage, hipStream_t stream);
+// The same two passes over the batch slots' pair records (requests whose rmap entry is
+// kNoReplaySlot).  Without watched edges (cw.ne == 0) no hop's replay-CSR entry is looked up.
+hipError_t launch_cross_count_pairs(const ReplayCSR& g, const PairChains& pc, const TraceIds& ids,
+                                    const TraceReqs& rq, const unsigned long long* w,
+                                    const int32_t* hops, const CrossWatch& cw, int64_t* lcnt,
+                                    int64_t* gcnt, unsigned long long* cnt, hipStream_t stream);
+hipError_t launch_cross_write_pairs(const ReplayCSR& g, const PairChains& pc, const TraceIds& ids,
+                                    const TraceReqs& rq, const int32_t* hops, const CrossWatch& cw,
+                                    const int64_t* loff, CrossRec* stage, hipStream_t stream);
+// copy a chunk's staged records to out at the call's offsets: request q's goff[ridx + 1] -
+// goff[ridx] records from stage[loff[q]] to out[goff[ridx]] when they end at or below cap
+hipError_t launch_cross_scatter(const TraceReqs& rq, const int64_t* goff, const int64_t* loff,
+                                const CrossRec* stage, CrossRec* out, int64_t cap,
+                                hipStream_t stream);
+
 hipError_t launch_pair_table_complete(int A, int64_t row0, int64_t rows, const double* elatAA,
                                       const double* elossAA, const double* vlossA, double2* out_lr,
                                       uint16_t* out_hops, double* out_rowmin,

@@ -77,6 +77,23 @@ class Random:
             pass
 
 
+# one record of Topology.link_crossings (ShdCrossing)
+CROSSING_DTYPE = np.dtype([("flow", np.int32), ("watch", np.int32), ("hop", np.int32),
+                           ("reverse", np.int32)])
+
+
+def crossings_by_watch(result):
+    """Invert a Topology.link_crossings result into {watch index: flow indices} -- every watch of
+    the call, the flows ascending, a flow once per record (host side: the records are already in
+    flow order, so a stable sort by watch is enough)."""
+    rec = result["records"]
+    order = np.argsort(rec["watch"], kind="stable")
+    watch, flow = rec["watch"][order], rec["flow"][order]
+    nw = len(result["count"])
+    cut = np.searchsorted(watch, np.arange(nw + 1))
+    return {k: flow[cut[k]:cut[k + 1]].copy() for k in range(nw)}
+
+
 def _b(s):
     return None if s is None else s.encode()
 
@@ -399,6 +416,59 @@ class Topology:
         if self._lib.shdtopo_link_load_stats(self._h, ctypes.byref(s)) != 0:
             raise RuntimeError("shdtopo_link_load_stats failed")
         return {k: getattr(s, k) for k, _ in L.ShdLoadStats._fields_}
+
+    # ---- link crossings ----
+    def link_crossings(self, src_ips, dst_ips, edges=(), vertices=(), weight=None, cap=None):
+        """shdtopo_link_crossings: the hops of the flows (src, dst, weight) that go over a watched
+        edge (``edges``: edge ids) or arrive at a watched vertex (``vertices``: vertex ids), along
+        the routes trace_routes reports.  Returns a dict: ``total``, the number of crossings;
+        ``offsets`` int64[n + 1], the running sum of the flows' record counts; ``records``, a
+        structured array (CROSSING_DTYPE: flow, watch, hop, reverse) ordered by flow, hop, edge
+        before vertex -- watch k < len(edges) is edges[k], len(edges) + k is vertices[k]; and per
+        watch ``count`` (its records) and ``weight`` (their flows' summed weight), uint64.
+        cap=None sizes the buffer first (a cap = 0 call); a smaller cap writes only the flows
+        whose records end at or below it (``records`` then has offsets[i + 1] <= cap entries)."""
+        s = np.ascontiguousarray(src_ips, dtype=np.uint32)
+        d = np.ascontiguousarray(dst_ips, dtype=np.uint32)
+        if s.shape != d.shape or s.ndim != 1:
+            raise ValueError("src_ips and dst_ips must be 1-D and of one length")
+        n = len(s)
+        w = None
+        if weight is not None:
+            w = np.ascontiguousarray(weight, dtype=np.uint64)
+            if w.shape != s.shape:
+                raise ValueError("weight must have one entry per flow")
+        we = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1)
+        wv = np.ascontiguousarray(vertices, dtype=np.int32).reshape(-1)
+        nw = len(we) + len(wv)
+        offsets = np.zeros(n + 1, np.int64)
+        count = np.zeros(max(nw, 1), np.uint64)
+        wsum = np.zeros(max(nw, 1), np.uint64)
+
+        def call(out, c):
+            return int(self._lib.shdtopo_link_crossings(
+                self._h, _p(s), _p(d), _p(w) if w is not None else None, n,
+                _p(we) if len(we) else None, len(we), _p(wv) if len(wv) else None, len(wv),
+                _p(offsets), _p(out) if c else None, c, _p(count), _p(wsum)))
+        if cap is None:
+            cap = call(None, 0)
+            if cap < 0:
+                raise RuntimeError("shdtopo_link_crossings failed: %d" % cap)
+        cap = int(cap)
+        records = np.zeros(max(cap, 1), CROSSING_DTYPE)
+        total = call(records, cap)
+        if total < 0:
+            raise RuntimeError("shdtopo_link_crossings failed: %d" % total)
+        fit = int(offsets[np.searchsorted(offsets, cap, side="right") - 1]) if cap else 0
+        return {"total": total, "offsets": offsets, "records": records[:fit],
+                "count": count[:nw], "weight": wsum[:nw]}
+
+    def link_crossings_stats(self):
+        """The last link_crossings' own counters (shdtopo_link_crossings_stats)."""
+        s = L.ShdCrossStats()
+        if self._lib.shdtopo_link_crossings_stats(self._h, ctypes.byref(s)) != 0:
+            raise RuntimeError("shdtopo_link_crossings_stats failed")
+        return {k: getattr(s, k) for k, _ in L.ShdCrossStats._fields_}
 
     def write_graphml(self, path):
         if self._lib.shdtopo_write_graphml(self._h, path.encode()) != 0:
