@@ -1,4 +1,5 @@
 """Shared test helpers: build the same topology for the product (HIP) and the oracle (CPU)."""
+import functools
 import os
 import tempfile
 
@@ -94,13 +95,18 @@ def graphml_doc(nodes, edges, directed=False):
 
 
 def random_topology_graphml(n_routers=600, n_poi=60, extra=2400, seed=3, integer=False,
-                            directed=False, parallel=0, lat_scale=1):
+                            directed=False, parallel=0, lat_scale=1, latency=None):
     """A connected router graph (a cycle, both directions when directed, plus `extra` random
     edges), poi vertices with an uplink (a pair of opposite edges when directed) and a self loop.
     `parallel` extra edges duplicate existing router edges with other latencies (multigraph).
-    Router latencies are U{1..100} x lat_scale (integer) or U[1, 100)."""
+    Router latencies are U{1..100} x lat_scale (integer) or U[1, 100).
+    `latency`: a function (rng, m) -> m latencies (a LATENCY_DOMAINS entry).  Every edge of the
+    graph -- router edges, poi uplinks and self loops -- then takes its latency from one draw of
+    it, made after the structure (same structure for every domain on one seed); without it the
+    uplinks are 5.0, the self loops 1.0 and the document is what it always was."""
     rng = np.random.default_rng(seed)
-    lat = ((lambda: int(rng.integers(1, 101)) * lat_scale) if integer
+    lat = ((lambda: 0.0) if latency is not None
+           else (lambda: int(rng.integers(1, 101)) * lat_scale) if integer
            else (lambda: rng.uniform(1, 100)))
     nodes = [("pop-%d" % i, "pop", 0.0) for i in range(n_routers)]
     nodes += [("poi-%d" % k, ("client", "relay", "server")[k % 3], rng.uniform(0, 0.05))
@@ -128,8 +134,94 @@ def random_topology_graphml(n_routers=600, n_poi=60, extra=2400, seed=3, integer
         if directed:
             edges.append((r, "poi-%d" % k, float(lat()), 0.0))
         edges.append(("poi-%d" % k, "poi-%d" % k, 1.0, 0.0))
+    if latency is not None:
+        vals = np.asarray(latency(rng, len(edges)), np.float64)
+        assert vals.shape == (len(edges),)
+        assert bool((vals > 0).all()) and bool(np.isfinite(vals).all())
+        edges = [(a, b, float(w), loss) for (a, b, _, loss), w in zip(edges, vals)]
     order = rng.permutation(len(edges))  # edge ids not grouped by vertex
     return graphml_doc(nodes, [edges[i] for i in order], directed)
+
+
+def _real(rng, m):
+    return rng.uniform(1, 100, m)
+
+
+def _int(rng, m):
+    return rng.integers(1, 101, m).astype(np.float64)
+
+
+def _bimodal(rng, m):
+    small, big, pick = rng.uniform(0.01, 0.1, m), rng.uniform(7e4, 2e5, m), rng.random(m)
+    return np.where(pick < 0.9, small, big)
+
+
+# Latency domains of the parity tests (test_latency_domains*.py): name -> function (rng, m).
+# The real and int families draw the same numbers at every scale on one seed, so a graph at
+# 2^k is the base graph with every latency multiplied by 2^k exactly.
+LATENCY_DOMAINS = {
+    "dec": lambda rng, m: rng.integers(1, 101, m) / 10,          # k/10: ties and near misses
+    "quarter": lambda rng, m: rng.integers(1, 401, m) / 4,       # k/4: exact non-integer ties
+    "logu": lambda rng, m: 10.0 ** rng.uniform(-3, 5, m),        # eight decades
+    "bimodal": _bimodal,                                         # 90 % < 0.1, 10 % > 7e4
+    "real": _real,
+    "real_dn30": lambda rng, m: _real(rng, m) * 2.0 ** -30,
+    "real_up30": lambda rng, m: _real(rng, m) * 2.0 ** 30,
+    "int": _int,
+    "int_dn30": lambda rng, m: _int(rng, m) * 2.0 ** -30,
+    "int_up30": lambda rng, m: _int(rng, m) * 2.0 ** 30,
+    "real_milli": lambda rng, m: _real(rng, m) * 1e-3,           # a non-dyadic rescale
+}
+TIE_FREE_DOMAINS = ("logu", "bimodal", "real_dn30", "real_up30", "real_milli")
+
+
+@functools.lru_cache(maxsize=None)
+def domain_graphml(domain, directed=False):
+    """The graph of the latency-domain tests: 3,000 routers, 15,000 extra edges, 100 poi, seed 3,
+    every latency from LATENCY_DOMAINS[domain]."""
+    return random_topology_graphml(n_routers=3000, n_poi=100, extra=15000, seed=3,
+                                   directed=directed, latency=LATENCY_DOMAINS[domain])
+
+
+DOMAIN_HOSTS = 120
+
+
+@functools.lru_cache(maxsize=None)
+def domain_oracle(domain, directed=False):
+    """The oracle's view of domain_graphml with the DOMAIN_HOSTS hosts of the tests attached by the
+    client / relay / server hints: (g, ips, verts, table), table = g.table(verts), computed once
+    and shared (never modified)."""
+    g = oracle.OGraph.from_graphml(domain_graphml(domain, directed))
+    otop = oracle.OracleTopology(g)
+    ips, verts = [], []
+    st = 1
+    hints = ("client", "relay", "server")
+    for k in range(DOMAIN_HOSTS):  # attach_hosts' stream, the oracle's half
+        st = (st * 1103515245 + 12345) & 0xFFFFFFFF
+        v, _ = otop.attach(host_ip(k + 1), st, type_hint=hints[k % 3])
+        ips.append(host_ip(k + 1))
+        verts.append(v)
+    return g, tuple(ips), tuple(verts), g.table(verts, nthreads=min(8, os.cpu_count() or 1))
+
+
+def parent_candidates(g, dist, src, ulps=8):
+    """Per vertex v != src: (exact, near) -- the in-neighbours u whose single f64 add d(u) + w
+    equals d(v) bit for bit (the reference's parent candidates), and those whose sum is not equal
+    but lies within `ulps` ulp of d(v) (equal as real numbers, different as doubles: not
+    candidates).  Self loops aside; undirected edges count from both ends."""
+    nl = g.eu != g.ev
+    u, v, w = g.eu[nl], g.ev[nl], g.elat[nl]
+    if not g.directed:
+        u, v, w = np.concatenate([u, v]), np.concatenate([v, u]), np.concatenate([w, w])
+    ok = (dist[u] >= 0) & (dist[v] >= 0) & (v != src)
+    u, v, w = u[ok], v[ok], w[ok]
+    s = dist[u] + w
+    eq = s == dist[v]
+    # ulp distance of two positive doubles = the difference of their bit patterns
+    gap = np.abs(s.view(np.int64) - dist[v].view(np.int64))
+    exact = np.bincount(v[eq], minlength=g.V)
+    near = np.bincount(v[~eq & (gap <= ulps)], minlength=g.V)
+    return exact, near
 
 
 def scipy_rows(graph, srcs, targets, directed=False):
