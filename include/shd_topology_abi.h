@@ -647,6 +647,25 @@ int shdtopo_link_crossings_stats(Topology* top, ShdCrossStats* out);
 int64_t shdtopo_export_csr(Topology* top, int32_t* perm, uint32_t* rowptr, uint32_t* col,
                            double* pot, uint32_t* treeParent);
 
+/* Test hook: one array of the graph preparation or of the last build's target
+ * preparation (4b) by name, copied to out (cap_bytes bytes).  Takes the build lock, prepares the
+ * graph if needed and drains the library's stream first (the target preparation is enqueued
+ * asynchronously).  Works for directed topologies.  Relabelled ids throughout.
+ *   graph:    perm, inv i32[V]; rowptr u32[V+1]; adj u32[4] per entry (in-rows when directed);
+ *             aloss f64 per entry; vloss, self_lat, self_loss, pot f64[V]; pi_max f64[1];
+ *             spt_parent u32[V]; spt u32[8] per vertex; adjk u32[4], kap f32 per entry; ksum
+ *             f32[probes] per vertex; kap0 f32[V]; kf_kap f64 per entry; hub_seg u32[2] per
+ *             segment; hub_multi u32[4] per row cut in several
+ *   directed: rowptr_in u32[V+1]; adj_out u32[4] per entry; pot_src f64[V]
+ *   targets:  tbits, tbits_eff, dead u32[(V+31)/32]; tleaf u32[8] per target; kfix f64[2V], the
+ *             final [K | Kt]
+ *   state:    i32[8] {adjk plain, flagged, resorted, leaf, kappa probes, kappa0 in the records,
+ *             hub segment length, grouping hubs}
+ * Returns the bytes copied; with out == NULL the array's size in bytes; -1: unknown name; -2:
+ * the array does not exist (complete topology, undirected topology's directed arrays, target
+ * arrays not built in this state); -3: cap_bytes too small. */
+int64_t shdtopo_export_prep(Topology* top, const char* name, void* out, int64_t cap_bytes);
+
 /* Copy the parsed graph into host arrays (document order; any pointer may be NULL):
  * eu, ev int32[E]; elat, eloss f64[E]; vloss f64[V].  Used by tools and oracle cross-checks. */
 int shdtopo_export_graph(Topology* top, int32_t* eu, int32_t* ev, double* elat, double* eloss,

@@ -157,6 +157,7 @@ SIGNATURES = {
                                                  ctypes.c_int, P, P, P]),
     "shdtopo_export_graph": (ctypes.c_int, [P, P, P, P, P, P]),
     "shdtopo_export_csr": (i64, [P, P, P, P, P, P]),
+    "shdtopo_export_prep": (i64, [P, cstr, P, i64]),
     "shdtopo_new_synthetic": (P, [P]),
     "shdtopo_synth_packets": (ctypes.c_int, [P, u64, i64, i64, u64, u64, P, P, P, P, P, P, P]),
 }

@@ -385,6 +385,8 @@ struct _Topology {
                               // iterate is exact)
     DevBuf<double> d_pot, d_kfA, d_kfB, d_kfPart;
     DevBuf<double> d_kfKap;   // the out-rows' static w - pi(y) of the kappa fixpoint
+    const double* kfFinal = nullptr;  // d_kfA or d_kfB: the last iterate [K | Kt] of the target
+                                      // preparation d_adjk carries (shdtopo_export_prep)
     bool kfKapReady = false;
     // the target-aware re-sort's scratch (KprimeScratch), kept: the first build's target
     // preparation allocates nothing (the background preparation sizes it)
@@ -1889,6 +1891,7 @@ int enqueue_rows(Topology* top, int64_t row0, int64_t row1, double2* out_lr, uin
                                                 top->d_pot.p, tbits, kin, sc, st));
                 }
                 HIPCHK(launch_kfix_store(top->d_adjk.p, nadjk, kin, st));
+                top->kfFinal = kin;
                 HIPCHK(hipEventRecord(top->evp1, st));
                 top->tpPending = true;
                 top->adjkTargets = tgt;
@@ -3253,6 +3256,7 @@ void release_prepared(Topology* top) {
                     &top->d_kfKap})
         b->release();
     top->kfKapReady = false;
+    top->kfFinal = nullptr;
     top->d_eu.release(); top->d_ev.release();
     top->d_kap.release(); top->d_ksum.release(); top->d_kap0.release();
     top->d_hseg.release(); top->d_hmulti.release(); top->d_kfChanged.release();
@@ -5249,6 +5253,78 @@ int64_t shdtopo_export_csr(Topology* top, int32_t* perm, uint32_t* rowptr, uint3
         for (size_t k = 0; k < nadj; k++) col[k] = rec[4 * k];
     }
     return (int64_t)nadj;
+}
+
+// Test hook: one prepared array by name (include/shd_topology_abi.h).  Host-kept arrays are copied
+// from the host, the others from the device after the library's stream has drained (the target
+// preparation of the last build is enqueued asynchronously).
+int64_t shdtopo_export_prep(Topology* top, const char* name, void* out, int64_t cap_bytes) {
+    if (!top || !name) return -1;
+    std::lock_guard<std::mutex> lk(top->buildMu);
+    if (top->isComplete) return -2;
+    int r = dev_init(top);
+    if (r) return r;
+    r = upload_csr(top);
+    if (r) return r;
+    HIPCHK(hipStreamSynchronize(top->stream));
+    const size_t V = (size_t)top->g.V, nadj = top->d_adj.p ? top->d_adj.n / 4 : 0;
+    const size_t words = (V + 31) / 32;
+    const bool dir = top->isDirected;
+    const bool leaf = top->d_tleaf.p && !top->leafFor.empty();
+    const bool tprep = top->adjkFlagged && top->kfFinal;
+    const HostPrep& hp = *top->hp;
+    const int32_t state[8] = {top->adjkPlain ? 1 : 0, top->adjkFlagged ? 1 : 0,
+                              top->adjkResorted ? 1 : 0, top->adjkLeaf ? 1 : 0, kKProbes,
+                              kKapInRec ? 1 : 0, (int32_t)kHubSeg, (int32_t)kGroupHubs};
+    struct Arr {
+        const char* name;
+        const void* host;
+        const void* dev;
+        size_t bytes;
+        bool ok;
+    };
+    const Arr arrs[] = {
+        {"perm", hp.perm.data(), nullptr, 4 * V, true},
+        {"inv", hp.inv.data(), nullptr, 4 * V, true},
+        {"rowptr", nullptr, top->d_rowptr.p, 4 * (V + 1), true},
+        {"adj", nullptr, top->d_adj.p, 16 * nadj, true},
+        {"aloss", nullptr, top->d_aloss.p, 8 * nadj, true},
+        {"vloss", nullptr, top->d_vloss.p, 8 * V, true},
+        {"self_lat", nullptr, top->d_selfLat.p, 8 * V, true},
+        {"self_loss", nullptr, top->d_selfLoss.p, 8 * V, true},
+        {"pot", hp.pot.data(), nullptr, 8 * V, true},
+        {"pi_max", &hp.piMax, nullptr, 8, true},
+        {"spt_parent", nullptr, top->d_sptPar.p, 4 * V, true},
+        {"spt", nullptr, top->d_spt.p, 32 * V, true},
+        {"adjk", nullptr, top->d_adjk.p, 16 * nadj, true},
+        {"kap", nullptr, top->d_kap.p, 4 * nadj, true},
+        {"ksum", nullptr, top->d_ksum.p, 4 * (size_t)kKProbes * V, true},
+        {"kap0", nullptr, top->d_kap0.p, 4 * V, true},
+        {"kf_kap", nullptr, top->d_kfKap.p, 8 * nadj, top->kfKapReady},
+        {"hub_seg", nullptr, top->d_hseg.p, sizeof(uint2) * (size_t)top->hsegN, true},
+        {"hub_multi", nullptr, top->d_hmulti.p, sizeof(uint4) * (size_t)top->hmultiN, true},
+        {"rowptr_in", nullptr, top->d_rowptrIn.p, 4 * (V + 1), dir},
+        {"adj_out", nullptr, top->d_adjo.p, 16 * nadj, dir},
+        {"pot_src", hp.potSrc.data(), nullptr, 8 * V, dir && hp.potSrc.size() == V},
+        {"tbits", nullptr, top->d_tbits.p, 4 * words, top->adjkFlagged && top->d_tbits.p},
+        {"tbits_eff", nullptr, top->d_tbitsEff.p, 4 * words, leaf},
+        {"dead", nullptr, top->d_dead.p, 4 * words, leaf},
+        {"tleaf", nullptr, top->d_tleaf.p, 32 * top->leafFor.size(), leaf},
+        {"kfix", nullptr, top->kfFinal, 16 * V, tprep},
+        {"state", state, nullptr, sizeof state, true},
+    };
+    for (const Arr& a : arrs) {
+        if (strcmp(a.name, name) != 0) continue;
+        if (!a.ok) return -2;
+        if (!out) return (int64_t)a.bytes;
+        if (cap_bytes < (int64_t)a.bytes) return -3;
+        if (a.bytes == 0) return 0;
+        if (a.host) memcpy(out, a.host, a.bytes);
+        else if (a.dev) HIPCHK(hipMemcpy(out, a.dev, a.bytes, hipMemcpyDeviceToHost));
+        else return -2;
+        return (int64_t)a.bytes;
+    }
+    return -1;
 }
 
 int shdtopo_export_graph(Topology* top, int32_t* eu, int32_t* ev, double* elat, double* eloss,

@@ -106,14 +106,23 @@ struct DevCSR {
     int32_t V = 0;
     int64_t nadj = 0;
     const uint32_t* rowptr = nullptr;     // rows of adjk (relaxation)
-    const uint32_t* adj = nullptr;  // 16-B AdjRec {u32 col, f32 pi(col) rounded up, f64 wt}
-    const uint32_t* adjk = nullptr; // the relaxation records, each row sorted by kappa = w - pi(col)
-    const float* kap = nullptr;     // kappa of adjk (f32 rounded down; -inf: pi unknown)
+    // 16-B AdjRec {u32 col, {f16 pi(col) rounded up, f16 kappa0(col) rounded down} (high, low
+    // half; kKapInRec = 0: f32 pi(col) rounded up), f64 w}, rows ascending by (neighbour, edge
+    // id).  Directed: the in-rows, whose field is not written (0); the out-rows' records with
+    // the field exist only as adjk's source
+    const uint32_t* adj = nullptr;
+    // the relaxation records: the out-rows' AdjRec, each row stably sorted by f32 kappa = w -
+    // pi(col) rounded down (from neighbour order), or for a target set by the target-aware key
+    // (from that order; the low half of the field is then f16 K(col) rounded down, +inf kept).
+    // Column word: bit 31 = the row is the column's h0-tree parent, bit 30 = target mark (tflags)
+    const uint32_t* adjk = nullptr;
+    const float* kap = nullptr;     // adjk's sort key (f32 rounded down; -inf: pi unknown)
     const float4* ksum = nullptr;   // per vertex: kappa at row positions 0, 1, 3, 7[, 15, 31, 63,
                                     // 127] (kKProbes floats, +inf past the row)
     const float* kap0 = nullptr;    // per vertex: smallest kappa of its row (+inf: empty row)
-    // per vertex, 32 B: {h0-tree parent, its slot in v's row, f64 w, f64 packet loss of that
-    // edge, pad} (one line per walk hop)
+    // per vertex, 32 B: {h0-tree parent, the adjacency position (into adj / aloss) of the
+    // parent's first entry in v's row (in-row when directed), f64 w, f64 packet loss of that
+    // edge, pad} (one line per walk hop); h0: {~0, ~0, ~0, ~0, 0...}
     const uint32_t* spt = nullptr;
     double piMax = 0.0;             // largest finite pi
     const double* aloss = nullptr;

@@ -332,8 +332,12 @@ struct TreeBest {
     unsigned long long du;
     uint32_t u, k;
 };
+// (d(u), u), then the adjacency position: of several tight parallel edges from one parent the
+// lowest slot (= lowest edge id) wins whichever lane or segment scanned it
 __device__ __forceinline__ bool tb_less(const TreeBest& a, const TreeBest& b) {
-    return a.du < b.du || (a.du == b.du && a.u < b.u);
+    if (a.du != b.du) return a.du < b.du;
+    if (a.u != b.u) return a.u < b.u;
+    return a.k < b.k;
 }
 
 __device__ __forceinline__ void tree_scan(const uint32_t* adj, const double* pot, uint32_t v,

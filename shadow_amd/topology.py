@@ -316,6 +316,55 @@ class Topology:
             raise RuntimeError("shdtopo_export_csr failed: %d" % r)
         return dict(perm=perm, rowptr=rowptr, col=col[:n], pot=pot, tree_parent=par)
 
+    # name -> (dtype, trailing shape) of shdtopo_export_prep's arrays
+    PREP_ARRAYS = {
+        "perm": (np.int32, ()), "inv": (np.int32, ()), "rowptr": (np.uint32, ()),
+        "adj": (np.uint32, (4,)), "aloss": (np.float64, ()), "vloss": (np.float64, ()),
+        "self_lat": (np.float64, ()), "self_loss": (np.float64, ()), "pot": (np.float64, ()),
+        "pi_max": (np.float64, ()), "spt_parent": (np.uint32, ()), "spt": (np.uint32, (8,)),
+        "adjk": (np.uint32, (4,)), "kap": (np.float32, ()), "ksum": (np.float32, None),
+        "kap0": (np.float32, ()), "kf_kap": (np.float64, ()), "hub_seg": (np.uint32, (2,)),
+        "hub_multi": (np.uint32, (4,)), "rowptr_in": (np.uint32, ()),
+        "adj_out": (np.uint32, (4,)), "pot_src": (np.float64, ()), "tbits": (np.uint32, ()),
+        "tbits_eff": (np.uint32, ()), "dead": (np.uint32, ()), "tleaf": (np.uint32, (8,)),
+        "kfix": (np.float64, ()), "state": (np.int32, ()),
+    }
+    PREP_STATE = ("adjk_plain", "flagged", "resorted", "leaf", "kprobes", "kap_in_rec",
+                  "hub_seg_len", "group_hubs")
+
+    def export_prep(self, names=None):
+        """Test hook (shdtopo_export_prep): the prepared arrays by name, relabelled ids -- every
+        array that exists in the topology's current state when names is None (an array that does
+        not: KeyError when asked for by name).  ``state`` comes back as a dict, ``ksum`` as
+        [V, probes]."""
+        out = {}
+        for name in (names if names is not None else self.PREP_ARRAYS):
+            dt, shape = self.PREP_ARRAYS[name]
+            n = int(self._lib.shdtopo_export_prep(self._h, name.encode(), None, 0))
+            if n == -2 and names is None:
+                continue
+            if n == -2:
+                raise KeyError(name)
+            if n < 0:
+                raise RuntimeError("shdtopo_export_prep(%s) failed: %d" % (name, n))
+            buf = np.empty(max(n, 1), np.uint8)
+            r = int(self._lib.shdtopo_export_prep(self._h, name.encode(), _p(buf), n))
+            if r != n:
+                raise RuntimeError("shdtopo_export_prep(%s) failed: %d" % (name, r))
+            out[name] = buf[:n].view(dt)
+        if "state" in out:
+            out["state"] = dict(zip(self.PREP_STATE, (int(x) for x in out["state"])))
+        for name, a in out.items():
+            if name == "state":
+                continue
+            shape = self.PREP_ARRAYS[name][1]
+            if shape is None:  # ksum: one row of probes per vertex
+                a = a.reshape(self.num_vertices, -1)
+            elif shape:
+                a = a.reshape((-1,) + shape)
+            out[name] = a
+        return out
+
     def replay_source(self, src, full=True):
         """Test hook (shdtopo_replay_source): the exact heap replay's (dist, parent vertex) from
         vertex `src`, original ids; full=False stops when every attached vertex is popped."""
