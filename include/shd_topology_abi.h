@@ -638,6 +638,92 @@ int64_t shdtopo_link_crossings(Topology* top, const uint32_t* srcIP, const uint3
                                /* u64[ne + nv] each, may be NULL */);
 int shdtopo_link_crossings_stats(Topology* top, ShdCrossStats* out);
 
+/* ---- link timeline: per-time-bin traffic on watched links and routers ----
+ * The trace, the load and the crossings ignore time.  The packets of a scheduler window carry an
+ * emission time (TopoPacketIn.now), and this call says when, inside the window, their bytes hit a
+ * watched link or router: for n flows (source host, destination host, weight, emission time now
+ * in ns), ne watched edges and nv watched vertices (as shdtopo_link_crossings) it sums the flows'
+ * weights per watch and time bin, without writing a single route out.
+ *
+ * Flow i's route is exactly the route shdtopo_trace_routes reports for (srcIP[i], dstIP[i]): the
+ * forward route of the source's row for the current attached set, each hop over the igraph_get_eid
+ * edge (the lowest id of a parallel group -- watching a higher id of the group reports nothing),
+ * the self loop for two hosts on one vertex or src == dst.  For hop k from vertex a to b over edge
+ * e let pre_k be the latency of hops 0 .. k - 1 and post_k that of hops 0 .. k, both accumulated
+ * from 0.0 by one IEEE add per hop in route order (the trace's accumulation; the 0 -> 1 override
+ * of a whole route's latency is not applied to prefixes).  With ns(x) = (uint64_t)ceil(x *
+ * 1000000.0), the conversion of topology_routePacketBatch, and u64 arithmetic,
+ *   enter_k = now[i] + ns(pre_k)      arrive_k = now[i] + ns(post_k)
+ *   e == watchEdge[j]    weight[i] goes to row j when the hop leaves eu[e] (every self loop and
+ *                        every arc of a directed topology), else to row ne + j (all zero on a
+ *                        directed topology), timed enter_k;
+ *   b == watchVertex[j]  weight[i] goes to row 2 ne + j, timed arrive_k: link load's vertexLoad
+ *                        rule -- every vertex of the route but its first; a self pair arrives
+ *                        once, over its loop.
+ * A hit with time t lands in outside[row][0] when t < t0, else in outside[row][1] when
+ * (t - t0) / binNs >= nbins, else in bins[row][(t - t0) / binNs].  bins is u64[(2 ne + nv) x
+ * nbins], row-major, outside u64[(2 ne + nv) x 2]; both are overwritten, not accumulated into.
+ * Sums are unsigned 64-bit and wrap, so the result does not depend on chunking, scheduling,
+ * "trace_batch" or which chain source served a flow.  now = NULL is 0 each: the bins are then
+ * "time since emission".  Summed over its bins and its outside pair a row holds watchWeight of
+ * shdtopo_link_crossings on the same flows and watches (fwd + rev for an edge watch).
+ *
+ * Returns the number of hits, in range or not: the total of shdtopo_link_crossings for the same
+ * flows and watches.  Requests with an unattached end, and unroutable ones, contribute nothing and
+ * are counted in the statistics.  ne + nv == 0 is valid: the call returns 0 and walks nothing.
+ * Negative on an error; -1: bad arguments -- NULL top; n, ne, nv or nbins negative; binNs == 0
+ * with nbins > 0; a NULL IP array with n > 0; a NULL watch array with a positive count; NULL bins
+ * with (2 ne + nv) x nbins > 0; an edge id outside [0, E) or a vertex id outside [0, V); a
+ * duplicate id within one watch list.
+ *
+ * Not modelled: the sender's Bernoulli drop (filter by `delivered` of the packet batch if wanted),
+ * the inter-host clamp and any queueing.  Shadow delivers a packet in one event at the
+ * destination; the intermediate times are this model's interpolation of that event along the
+ * route, not times Shadow itself would ever observe.
+ *
+ * SSSP topologies: chunks and chain sources as shdtopo_link_crossings; option "load_walk" has no
+ * meaning here.  A flow without a hit costs one walk; a flow with one parks its hops (8 B each) in
+ * device memory and is walked again source -> destination.  Complete topologies
+ * are answered on the host from the parsed graph (one hop over the direct edge: enter = now,
+ * arrive = now + ns(0.0 + latency)): no device is used.  A multi-device topology runs on its first
+ * device.  Like a trace, a load and the crossings, the call holds the build lock, materialises no
+ * lazy row, pushes no minimum, neither invalidates nor rebuilds the table and leaves ShdStats and
+ * the trace, load and crossings statistics as they were. */
+typedef struct {
+    double  total_ms;        /* wall time of the call */
+    double  replay_ms;       /* event time of its heap-replay launches only */
+    double  kernel_ms;       /* event time of everything but the replay and the keep launches */
+    double  ids_ms;          /* edge-id upload, first trace/load/crossings/timeline, else 0 */
+    double  batch_ms;        /* event time of the batch kernel's keep launches */
+    int64_t requests;        /* n */
+    int64_t routed;          /* requests whose route was walked */
+    int64_t unattached;      /* requests with an unattached end (contribute nothing) */
+    int64_t broken;          /* unroutable / broken chain / self pair without a self loop */
+    int64_t sources;         /* distinct source vertices of the call, either path */
+    int64_t chunks;          /* source chunks */
+    int64_t batch_sources;   /* distinct sources answered from the batch kernel's parent records */
+    int64_t batch_fallback;  /* sources that ran a keep launch and then went to the heap replay */
+    int64_t hits;            /* the call's return value */
+    int64_t flows_hit;       /* flows with at least one hit */
+    int64_t in_range;        /* hits (not weights) that landed in a bin */
+    int64_t before;          /* hits before t0 */
+    int64_t after;           /* hits at or after the last bin */
+    int64_t staged_hops;     /* hops parked in device memory (flows with a hit, self pairs aside) */
+} ShdTimelineStats;
+
+int64_t shdtopo_link_timeline(Topology* top, const uint32_t* srcIP, const uint32_t* dstIP,
+                              const uint64_t* weight /* NULL: 1 each */,
+                              const uint64_t* now /* ns; NULL: 0 each = "time since emission" */,
+                              int64_t n,
+                              const int32_t* watchEdge, int64_t ne /* edge ids, document order */,
+                              const int32_t* watchVertex, int64_t nv /* original vertex ids */,
+                              uint64_t t0, uint64_t binNs, int64_t nbins,
+                              uint64_t* bins /* u64[(2 ne + nv) * nbins], row-major; may be NULL
+                                                iff that is 0 */,
+                              uint64_t* outside /* u64[(2 ne + nv) * 2]: {before t0, at or after
+                                                   the last bin}; may be NULL */);
+int shdtopo_link_timeline_stats(Topology* top, ShdTimelineStats* out);
+
 /* Test hook: the device graph preparation (topo_prep.hip) read back -- perm
  * int32[V] (relabelled -> original vertex), rowptr u32[V+1], the adjacency columns u32[2E']
  * (relabelled ids, rows ascending by neighbour), pi f64[V] (= d(h0, .), relabelled ids) and the

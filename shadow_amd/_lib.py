@@ -94,6 +94,14 @@ class ShdCrossStats(ctypes.Structure):
                 ("batch_ms", dbl), ("batch_sources", i64), ("batch_fallback", i64)]
 
 
+class ShdTimelineStats(ctypes.Structure):
+    _fields_ = [("total_ms", dbl), ("replay_ms", dbl), ("kernel_ms", dbl), ("ids_ms", dbl),
+                ("batch_ms", dbl), ("requests", i64), ("routed", i64), ("unattached", i64),
+                ("broken", i64), ("sources", i64), ("chunks", i64), ("batch_sources", i64),
+                ("batch_fallback", i64), ("hits", i64), ("flows_hit", i64), ("in_range", i64),
+                ("before", i64), ("after", i64), ("staged_hops", i64)]
+
+
 class ShdSynthParams(ctypes.Structure):
     _fields_ = [("seed", u64), ("n_routers", i64), ("n_poi", i64), ("n_edges", i64),
                 ("integer_latency", ctypes.c_int), ("alpha", dbl), ("directed", ctypes.c_int)]
@@ -152,6 +160,8 @@ SIGNATURES = {
     "shdtopo_link_load_stats": (ctypes.c_int, [P, P]),
     "shdtopo_link_crossings": (i64, [P, P, P, P, i64, P, i64, P, i64, P, P, i64, P, P]),
     "shdtopo_link_crossings_stats": (ctypes.c_int, [P, P]),
+    "shdtopo_link_timeline": (i64, [P, P, P, P, P, i64, P, i64, P, i64, u64, u64, i64, P, P]),
+    "shdtopo_link_timeline_stats": (ctypes.c_int, [P, P]),
     "shdtopo_test_segsort": (ctypes.c_int, [P, i64, P, i64, ctypes.c_int, P, P]),
     "shdtopo_test_batch_layout": (ctypes.c_int, [P, i64, dbl, ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_int, P, P, P]),

@@ -472,6 +472,7 @@ struct _Topology {
                                  // DESIGN.md 3.7), 0 = the leaf-to-root tree accumulation
     ShdLoadStats loadStats{};    // the last call's own counters
     ShdCrossStats crossStats{};  // link crossings (shdtopo_link_crossings, topo_cross.hip)
+    ShdTimelineStats timelineStats{};  // link timeline (shdtopo_link_timeline, topo_timeline.hip)
 
     // multi-GPU build inside the library (one Shadow process): device d builds
     // rows [d*R, (d+1)*R) with its own stream / workspace (a peer Topology on that device),
@@ -4855,6 +4856,56 @@ struct WatchSet {
     int32_t vertex(int32_t v) const { return find(vids, vidx, v); }
 };
 
+// The device image of a watch set (CrossWatch, its totals aside): bits by edge id and by
+// relabelled vertex, the sorted ids for the hits.
+struct DevWatch {
+    DevBuf<uint32_t> d_ebits, d_vbits;
+    DevBuf<int32_t> d_eids, d_eidx, d_vids, d_vidx;
+    CrossWatch cw;
+    int upload(Topology* top, const WatchSet& wset) {
+        const size_t V = (size_t)top->g.V, E = (size_t)top->g.E;
+        const size_t ne = wset.eids.size(), nvw = wset.vids.size();
+        std::vector<uint32_t> ebits(E / 32 + 1, 0u), vbits(V / 32 + 1, 0u);
+        for (int32_t e : wset.eids) ebits[(size_t)e >> 5] |= 1u << (e & 31);
+        std::vector<std::pair<int32_t, int32_t>> rv(nvw);
+        for (size_t k = 0; k < nvw; k++) {
+            const int32_t x = top->hp->inv[(size_t)wset.vids[k]];
+            vbits[(size_t)x >> 5] |= 1u << (x & 31);
+            rv[k] = {x, wset.vidx[k]};
+        }
+        std::sort(rv.begin(), rv.end());
+        std::vector<int32_t> vids(nvw), vidx(nvw);
+        for (size_t k = 0; k < nvw; k++) {
+            vids[k] = rv[k].first;
+            vidx[k] = rv[k].second;
+        }
+        HIPCHK(d_ebits.ensure(ebits.size())); HIPCHK(d_vbits.ensure(vbits.size()));
+        HIPCHK(d_eids.ensure(std::max<size_t>(1, ne))); HIPCHK(d_eidx.ensure(std::max<size_t>(1, ne)));
+        HIPCHK(d_vids.ensure(std::max<size_t>(1, nvw))); HIPCHK(d_vidx.ensure(std::max<size_t>(1, nvw)));
+        HIPCHK(hipMemcpy(d_ebits.p, ebits.data(), 4 * ebits.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_vbits.p, vbits.data(), 4 * vbits.size(), hipMemcpyHostToDevice));
+        if (ne) {
+            HIPCHK(hipMemcpy(d_eids.p, wset.eids.data(), 4 * ne, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(d_eidx.p, wset.eidx.data(), 4 * ne, hipMemcpyHostToDevice));
+        }
+        if (nvw) {
+            HIPCHK(hipMemcpy(d_vids.p, vids.data(), 4 * nvw, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(d_vidx.p, vidx.data(), 4 * nvw, hipMemcpyHostToDevice));
+        }
+        cw.ebits = d_ebits.p;
+        cw.vbits = d_vbits.p;
+        cw.eids = d_eids.p;
+        cw.eidx = d_eidx.p;
+        cw.vids = d_vids.p;
+        cw.vidx = d_vidx.p;
+        cw.ne = (int32_t)ne;
+        cw.nv = (int32_t)nvw;
+        cw.E = (int64_t)E;
+        cw.eu = top->d_eu.p;
+        return 0;
+    }
+};
+
 // Complete topologies, on the host as load_complete: one hop (hop 0) over the direct edge, a self
 // pair over the loop; the edge record before the vertex record.
 int64_t cross_complete(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
@@ -4904,56 +4955,20 @@ int64_t cross_replay(Topology* top, const std::vector<int32_t>& sv, const std::v
     int r = group_replay_requests(top, sv, dv, n, &cs->ids_ms, false, R);
     if (r) return r;
     hipStream_t st = top->stream;
-    const size_t nv = R.nv, mmax = R.mmax, V = (size_t)top->g.V, E = (size_t)top->g.E;
+    const size_t nv = R.nv, mmax = R.mmax;
     const size_t ne = wset.eids.size(), nvw = wset.vids.size(), nw = ne + nvw;
     cs->sources = R.nsrc;
 
-    // the watch set: bits by edge id and by relabelled vertex, the sorted ids for the hits
-    std::vector<uint32_t> ebits(E / 32 + 1, 0u), vbits(V / 32 + 1, 0u);
-    for (int32_t e : wset.eids) ebits[(size_t)e >> 5] |= 1u << (e & 31);
-    std::vector<std::pair<int32_t, int32_t>> rv(nvw);
-    for (size_t k = 0; k < nvw; k++) {
-        const int32_t x = top->hp->inv[(size_t)wset.vids[k]];
-        vbits[(size_t)x >> 5] |= 1u << (x & 31);
-        rv[k] = {x, wset.vidx[k]};
-    }
-    std::sort(rv.begin(), rv.end());
-    std::vector<int32_t> vids(nvw), vidx(nvw);
-    for (size_t k = 0; k < nvw; k++) {
-        vids[k] = rv[k].first;
-        vidx[k] = rv[k].second;
-    }
-    DevBuf<uint32_t> d_ebits, d_vbits;
-    DevBuf<int32_t> d_eids, d_eidx, d_vids, d_vidx, d_hops;
+    DevWatch dw;
+    r = dw.upload(top, wset);
+    if (r) return r;
+    DevBuf<int32_t> d_hops;
     DevBuf<unsigned long long> d_w, d_wcount, d_wweight, d_cnt, d_pcnt, d_ccnt;
     DevBuf<int64_t> d_gcnt, d_goff, d_lcnt, d_coff, d_loff;
-    HIPCHK(d_ebits.ensure(ebits.size())); HIPCHK(d_vbits.ensure(vbits.size()));
-    HIPCHK(d_eids.ensure(std::max<size_t>(1, ne))); HIPCHK(d_eidx.ensure(std::max<size_t>(1, ne)));
-    HIPCHK(d_vids.ensure(std::max<size_t>(1, nvw))); HIPCHK(d_vidx.ensure(std::max<size_t>(1, nvw)));
     HIPCHK(d_wcount.ensure(nw)); HIPCHK(d_wweight.ensure(nw));
-    HIPCHK(hipMemcpy(d_ebits.p, ebits.data(), 4 * ebits.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_vbits.p, vbits.data(), 4 * vbits.size(), hipMemcpyHostToDevice));
-    if (ne) {
-        HIPCHK(hipMemcpy(d_eids.p, wset.eids.data(), 4 * ne, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_eidx.p, wset.eidx.data(), 4 * ne, hipMemcpyHostToDevice));
-    }
-    if (nvw) {
-        HIPCHK(hipMemcpy(d_vids.p, vids.data(), 4 * nvw, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_vidx.p, vidx.data(), 4 * nvw, hipMemcpyHostToDevice));
-    }
     HIPCHK(hipMemsetAsync(d_wcount.p, 0, 8 * nw, st));
     HIPCHK(hipMemsetAsync(d_wweight.p, 0, 8 * nw, st));
-    CrossWatch cw;
-    cw.ebits = d_ebits.p;
-    cw.vbits = d_vbits.p;
-    cw.eids = d_eids.p;
-    cw.eidx = d_eidx.p;
-    cw.vids = d_vids.p;
-    cw.vidx = d_vidx.p;
-    cw.ne = (int32_t)ne;
-    cw.nv = (int32_t)nvw;
-    cw.E = (int64_t)E;
-    cw.eu = top->d_eu.p;
+    CrossWatch cw = dw.cw;
     cw.wcount = d_wcount.p;
     cw.wweight = d_wweight.p;
 
@@ -5059,6 +5074,179 @@ int64_t cross_replay(Topology* top, const std::vector<int32_t>& sv, const std::v
     cs->flows_hit = (int64_t)ccnt[CR_FLOWS];
     if ((int64_t)ccnt[CR_RECORDS] != total) return -3;
     return total;
+}
+
+// ---------------------------------------------------------------------------------------------
+// link timeline (include/shd_topology_abi.h shdtopo_link_timeline; kernels in topo_timeline.hip)
+// ---------------------------------------------------------------------------------------------
+// the packet kernel's conversion (topo_kernels.hip): milliseconds -> nanoseconds, rounded up
+uint64_t lat_ns(double ms) { return (uint64_t)std::ceil(ms * 1000000.0); }
+
+// where a hit lands, and its count
+struct TimelineOut {
+    uint64_t t0, binNs;
+    int64_t nbins;
+    uint64_t* bins;
+    uint64_t* outside;
+    void add(int64_t row, uint64_t t, uint64_t w, ShdTimelineStats* ts) const {
+        ts->hits++;
+        if (t < t0) {
+            ts->before++;
+            if (outside) outside[2 * row] += w;
+            return;
+        }
+        if (nbins > 0 && (t - t0) / binNs < (uint64_t)nbins) {
+            ts->in_range++;
+            bins[row * nbins + (int64_t)((t - t0) / binNs)] += w;
+            return;
+        }
+        ts->after++;
+        if (outside) outside[2 * row + 1] += w;
+    }
+};
+
+// Complete topologies, on the host as cross_complete: one hop over the direct edge, entered at the
+// emission time; a self pair over the loop.
+int64_t timeline_complete(Topology* top, const std::vector<int32_t>& sv,
+                          const std::vector<int32_t>& dv, const uint64_t* weight,
+                          const uint64_t* now, int64_t n, const WatchSet& ws,
+                          const TimelineOut& to, ShdTimelineStats* ts) {
+    const HostGraph& g = top->g;
+    const int64_t ne = (int64_t)ws.eids.size();
+    const std::vector<int32_t> pe = complete_pair_eids(top, sv, dv, n);
+    for (int64_t i = 0; i < n; i++) {
+        const int32_t s = sv[(size_t)i], d = dv[(size_t)i];
+        if (s < 0 || d < 0) continue;  // counted by the caller
+        const int32_t e = pe[(size_t)i];
+        if (e < 0) {
+            ts->broken++;
+            continue;
+        }
+        ts->routed++;
+        const uint64_t w = weight ? weight[i] : 1, t = now ? now[i] : 0;
+        const int64_t h0 = ts->hits;
+        const int32_t ke = ws.edge(e), kv = ws.vertex(d);
+        if (ke >= 0) to.add(s != g.eu[(size_t)e] ? ne + ke : ke, t, w, ts);
+        double lat = 0.0;
+        lat += g.elat[(size_t)e];
+        if (kv >= 0) to.add(ne + kv, t + lat_ns(lat), w, ts);
+        if (ts->hits > h0) ts->flows_hit++;
+    }
+    return ts->hits;
+}
+
+// SSSP topologies: the distinct sources in chunks -- chains from the batch kernel's pair records
+// or the replay (chunk_chains), whatever "load_walk" says -- link load's validation, then the mark
+// and time walks of topo_timeline.hip; the hops of the flows with a hit are staged per chunk and
+// die with it, the bins are the call's and copied out once the last chunk is walked
+int64_t timeline_replay(Topology* top, const std::vector<int32_t>& sv,
+                        const std::vector<int32_t>& dv, const uint64_t* weight,
+                        const uint64_t* now, int64_t n, const WatchSet& wset,
+                        const TimelineOut& to, ShdTimelineStats* ts) {
+    ReplayReqs R;
+    int r = group_replay_requests(top, sv, dv, n, &ts->ids_ms, false, R);
+    if (r) return r;
+    hipStream_t st = top->stream;
+    const size_t nv = R.nv, mmax = R.mmax;
+    const size_t rows = 2 * wset.eids.size() + wset.vids.size();
+    const size_t nacc = rows * ((size_t)to.nbins + 2);
+    ts->sources = R.nsrc;
+
+    DevWatch dw;
+    r = dw.upload(top, wset);
+    if (r) return r;
+    std::vector<unsigned long long> rw(nv, 1ull), rnow(nv, 0ull);
+    if (weight)
+        for (size_t q = 0; q < nv; q++) rw[q] = weight[R.order[q]];
+    if (now)
+        for (size_t q = 0; q < nv; q++) rnow[q] = now[R.order[q]];
+    DevBuf<int32_t> d_hops;
+    DevBuf<unsigned long long> d_w, d_now, d_acc, d_cnt, d_pcnt, d_tcnt;
+    DevBuf<int64_t> d_seg, d_coff;
+    DevBuf<uint2> d_stage;
+    HIPCHK(d_w.ensure(nv)); HIPCHK(d_now.ensure(nv));
+    HIPCHK(d_hops.ensure(nv));
+    HIPCHK(d_acc.ensure(nacc));
+    HIPCHK(d_cnt.ensure(LD_COUNT)); HIPCHK(d_pcnt.ensure(LD_COUNT)); HIPCHK(d_tcnt.ensure(TL_COUNT));
+    HIPCHK(d_seg.ensure(mmax + 1)); HIPCHK(d_coff.ensure(mmax + 1));
+    HIPCHK(hipMemcpy(d_w.p, rw.data(), 8 * nv, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_now.p, rnow.data(), 8 * nv, hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(d_acc.p, 0, 8 * nacc, st));
+    HIPCHK(hipMemsetAsync(d_cnt.p, 0, 8 * LD_COUNT, st));
+    HIPCHK(hipMemsetAsync(d_tcnt.p, 0, 8 * TL_COUNT, st));
+    TimeBins tb;
+    tb.acc = d_acc.p;
+    tb.rows = (int64_t)rows;
+    tb.nbins = to.nbins;
+    tb.t0 = to.t0;
+    tb.binNs = to.binNs;
+
+    unsigned long long pcnt[LD_COUNT] = {};  // the pair walks' validation, as load_replay
+    for (int s0 = 0; s0 < R.nsrc; s0 += R.chunk) {
+        const int s1 = std::min(R.nsrc, s0 + R.chunk);
+        TraceReqs rq = R.reqs(s0, s1);
+        const size_t q0 = R.srcStart[(size_t)s0], m = (size_t)rq.n;
+        HIPCHK(hipMemsetAsync(d_seg.p, 0, 8 * (m + 1), st));
+        r = chunk_chains(top, R, s0, s1, &rq,
+                         [&](const TraceReqs& q, bool) {
+                             HIPCHK(hipMemsetAsync(d_pcnt.p, 0, 8 * LD_COUNT, st));
+                             HIPCHK(launch_load_validate_pairs(R.csr, R.pc, q, d_w.p + q0,
+                                                               d_hops.p + q0, d_pcnt.p,
+                                                               R.d_broken.p, st));
+                             return 0;
+                         },
+                         &ts->batch_ms, &ts->batch_sources, &ts->batch_fallback);
+        if (r) return r;
+        // both chain sources write the same segments and bins: each takes its requests
+        const bool pairs = R.mixed && R.nfall < s1 - s0;
+        unsigned long long c[LD_COUNT] = {};
+        if (pairs) {
+            HIPCHK(hipMemcpyAsync(c, d_pcnt.p, 8 * LD_COUNT, hipMemcpyDeviceToHost, st));
+            HIPCHK(launch_timeline_mark_pairs(R.csr, R.pc, R.ids, rq, d_hops.p + q0, dw.cw, d_seg.p,
+                                              d_tcnt.p, st));
+        }
+        if (R.nfall > 0) {
+            HIPCHK(launch_load_validate(R.csr, R.ws, rq, d_w.p + q0, d_hops.p + q0, d_cnt.p, st));
+            HIPCHK(launch_timeline_mark(R.csr, R.ws, R.ids, rq, d_hops.p + q0, dw.cw, d_seg.p,
+                                        d_tcnt.p, st));
+        }
+        HIPCHK(trace_exclusive_scan(d_seg.p, d_coff.p, (int64_t)m + 1, st));
+        int64_t tot = 0;
+        HIPCHK(hipMemcpy(&tot, d_coff.p + m, 8, hipMemcpyDeviceToHost));
+        HIPCHK(d_stage.ensure((size_t)std::max<int64_t>(1, tot)));
+        if (pairs && tot > 0)
+            HIPCHK(launch_timeline_time_pairs(R.csr, R.pc, R.ids, rq, d_w.p + q0, d_now.p + q0,
+                                              d_hops.p + q0, dw.cw, d_coff.p, d_stage.p, tb,
+                                              d_tcnt.p, st));
+        if (R.nfall > 0 && tot > 0)
+            HIPCHK(launch_timeline_time(R.csr, R.ws, R.ids, rq, d_w.p + q0, d_now.p + q0,
+                                        d_hops.p + q0, dw.cw, d_coff.p, d_stage.p, tb, d_tcnt.p, st));
+        HIPCHK(hipEventRecord(R.ev.e[2], st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int i = 0; i < LD_COUNT; i++) pcnt[i] += c[i];
+        r = chunk_times(R, &ts->replay_ms, &ts->kernel_ms);
+        if (r) return r;
+        ts->chunks++;
+    }
+
+    unsigned long long cnt[LD_COUNT] = {}, tcnt[TL_COUNT] = {};
+    std::vector<unsigned long long> acc(nacc);
+    HIPCHK(hipMemcpyAsync(cnt, d_cnt.p, 8 * LD_COUNT, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(tcnt, d_tcnt.p, 8 * TL_COUNT, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(acc.data(), d_acc.p, 8 * nacc, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const size_t nb = rows * (size_t)to.nbins;
+    if (nb) std::copy(acc.begin(), acc.begin() + nb, to.bins);
+    if (to.outside) std::copy(acc.begin() + nb, acc.end(), to.outside);
+    ts->routed = (int64_t)(cnt[LD_ROUTED] + pcnt[LD_ROUTED]);
+    ts->broken = (int64_t)(cnt[LD_BROKEN] + pcnt[LD_BROKEN]);
+    ts->flows_hit = (int64_t)tcnt[TL_FLOWS];
+    ts->in_range = (int64_t)tcnt[TL_IN];
+    ts->before = (int64_t)tcnt[TL_BEFORE];
+    ts->after = (int64_t)tcnt[TL_AFTER];
+    ts->staged_hops = (int64_t)tcnt[TL_STAGED];
+    ts->hits = ts->in_range + ts->before + ts->after;
+    return ts->hits;
 }
 
 }  // namespace
@@ -5196,6 +5384,59 @@ int shdtopo_link_crossings_stats(Topology* top, ShdCrossStats* out) {
     if (!top || !out) return -1;
     std::lock_guard<std::mutex> lk(top->buildMu);
     *out = top->crossStats;
+    return 0;
+}
+
+int64_t shdtopo_link_timeline(Topology* top, const uint32_t* srcIP, const uint32_t* dstIP,
+                              const uint64_t* weight, const uint64_t* now, int64_t n,
+                              const int32_t* watchEdge, int64_t ne, const int32_t* watchVertex,
+                              int64_t nv, uint64_t t0, uint64_t binNs, int64_t nbins,
+                              uint64_t* bins, uint64_t* outside) {
+    if (!top || n < 0 || n > 0x7FFFFFFE || ne < 0 || nv < 0 || nbins < 0) return -1;
+    if (nbins > 0 && binNs == 0) return -1;
+    if (n > 0 && (!srcIP || !dstIP)) return -1;
+    if ((ne > 0 && !watchEdge) || (nv > 0 && !watchVertex)) return -1;
+    if (ne > top->g.E || nv > top->g.V) return -1;  // (more ids than there are: a duplicate)
+    const int64_t rows = 2 * ne + nv;
+    if (nbins > 0 && rows > (int64_t)0x7FFFFFFF / nbins) return -1;  // (a device buffer of rows x bins)
+    if (rows * nbins > 0 && !bins) return -1;
+    const auto tstart = std::chrono::steady_clock::now();
+    std::lock_guard<std::mutex> lk(top->buildMu);
+    WatchSet ws;
+    if (!ws.init(top->g, watchEdge, ne, watchVertex, nv)) return -1;
+    ShdTimelineStats ts{};
+    ts.requests = n;
+    compute_geometry(top);
+    // the outputs are overwritten, not accumulated into
+    if (bins) std::fill(bins, bins + (size_t)(rows * nbins), (uint64_t)0);
+    if (outside) std::fill(outside, outside + (size_t)(2 * rows), (uint64_t)0);
+    // both ends on a vertex of the current attached set, as a trace
+    std::vector<int32_t> sv((size_t)n), dv((size_t)n);
+    int64_t nvalid = 0;
+    for (int64_t i = 0; i < n; i++) {
+        int32_t s = vertex_of_ip(top, srcIP[i]), d = vertex_of_ip(top, dstIP[i]);
+        if (s >= 0 && (s >= top->g.V || top->colOf[(size_t)s] < 0)) s = -1;
+        if (d >= 0 && (d >= top->g.V || top->colOf[(size_t)d] < 0)) d = -1;
+        sv[(size_t)i] = s;
+        dv[(size_t)i] = d;
+        if (s >= 0 && d >= 0) nvalid++;
+    }
+    ts.unattached = n - nvalid;
+    const TimelineOut to{t0, binNs, nbins, bins, outside};
+    int64_t hits = 0;
+    if (rows == 0) hits = 0;  // an empty watch set: nothing to walk for
+    else if (top->isComplete) hits = timeline_complete(top, sv, dv, weight, now, n, ws, to, &ts);
+    else if (nvalid > 0) hits = timeline_replay(top, sv, dv, weight, now, n, ws, to, &ts);
+    if (hits < 0) ts.hits = 0;
+    ts.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tstart).count();
+    top->timelineStats = ts;
+    return hits;
+}
+
+int shdtopo_link_timeline_stats(Topology* top, ShdTimelineStats* out) {
+    if (!top || !out) return -1;
+    std::lock_guard<std::mutex> lk(top->buildMu);
+    *out = top->timelineStats;
     return 0;
 }
 

@@ -32,6 +32,7 @@
 #include <cstdint>
 
 #include "topo_chain.h"
+#include "topo_watch.h"
 
 namespace shdtopo {
 
@@ -50,31 +51,7 @@ unsigned grid_for(int64_t n) {
     return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + kTB - 1) / kTB, 65536));
 }
 
-// position of x in the ascending ids[0..n), -1 when absent
-__device__ __forceinline__ int32_t watch_find(const int32_t* __restrict__ ids, int32_t n,
-                                              int32_t x) {
-    int32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        const int32_t y = ids[mid];
-        if (y == x) return mid;
-        if (y < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return -1;
-}
-// watch index of edge e / relabelled vertex v, -1 when not watched (or e is no edge)
-__device__ __forceinline__ int32_t edge_watch(const CrossWatch& cw, int32_t e) {
-    if ((uint32_t)e >= (uint64_t)cw.E) return -1;
-    if (!((cw.ebits[(uint32_t)e >> 5] >> (e & 31)) & 1u)) return -1;
-    const int32_t i = watch_find(cw.eids, cw.ne, e);
-    return i < 0 ? -1 : cw.eidx[i];
-}
-__device__ __forceinline__ int32_t vertex_watch(const CrossWatch& cw, uint32_t v) {
-    if (!((cw.vbits[v >> 5] >> (v & 31)) & 1u)) return -1;
-    const int32_t i = watch_find(cw.vids, cw.nv, (int32_t)v);
-    return i < 0 ? -1 : cw.vidx[i];
-}
+// (the watch tests -- watch_find, edge_watch, vertex_watch -- are topo_watch.h's)
 __device__ __forceinline__ void watch_add(const CrossWatch& cw, int32_t k, u64 w) {
     atomicAdd(&cw.wcount[k], 1ull);
     atomicAdd(&cw.wweight[k], w);

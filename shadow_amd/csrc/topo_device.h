@@ -537,6 +537,48 @@ hipError_t launch_cross_scatter(const TraceReqs& rq, const int64_t* goff, const 
                                 const CrossRec* stage, CrossRec* out, int64_t cap,
                                 hipStream_t stream);
 
+// ---- link timeline (topo_timeline.hip): per-time-bin traffic on watched edges / vertices ----
+// The bins of one call.  Rows: [0, ne) an edge watch's hops leaving eu[e], [ne, 2 ne) its other
+// hops, [2 ne, 2 ne + nv) the vertex watches' arrivals.  acc: u64[rows x nbins], row-major, then
+// the `outside` pairs u64[rows x 2] {before t0, at or after the last bin}; zeroed by the caller.
+struct TimeBins {
+    unsigned long long* acc = nullptr;
+    int64_t rows = 0, nbins = 0;
+    unsigned long long t0 = 0, binNs = 0;  // ns; binNs > 0 when nbins > 0
+};
+// counters of one call (u64 words, zeroed by the caller); the hits are IN + BEFORE + AFTER
+enum { TL_FLOWS = 0, TL_IN, TL_BEFORE, TL_AFTER, TL_STAGED, TL_COUNT };
+// Mark: request q (hops[q] from launch_load_validate[_pairs]) walks rdst -> rsrc until its first
+// hit: seg[q] = hops[q] when a hop goes over a watched edge or arrives at a watched vertex, else 0
+// (cw.wcount / cw.wweight are not used); the flows with a hit and their hops (self pairs aside:
+// they are not staged) into cnt[TL_FLOWS / TL_STAGED].
+hipError_t launch_timeline_mark(const ReplayCSR& g, const ReplayWs& ws, const TraceIds& ids,
+                                const TraceReqs& rq, const int32_t* hops, const CrossWatch& cw,
+                                int64_t* seg, unsigned long long* cnt, hipStream_t stream);
+// Time: a request with a segment [loff[q], loff[q + 1]) of hops[q] entries parks {replay-CSR
+// entry, arrival vertex} of its hops there, back to front, then runs front to back: the prefix
+// latency by one IEEE add per hop from 0.0, each hit's weight w[q] into the bin of now[q] + ns(the
+// prefix before the hop) for an edge watch, + ns(the prefix with it) for a vertex watch; the hit
+// counts into cnt[TL_IN / TL_BEFORE / TL_AFTER].
+hipError_t launch_timeline_time(const ReplayCSR& g, const ReplayWs& ws, const TraceIds& ids,
+                                const TraceReqs& rq, const unsigned long long* w,
+                                const unsigned long long* now, const int32_t* hops,
+                                const CrossWatch& cw, const int64_t* loff, uint2* stage,
+                                const TimeBins& tb, unsigned long long* cnt, hipStream_t stream);
+// The same two passes over the batch slots' pair records (requests whose rmap entry is
+// kNoReplaySlot).  Without watched edges (cw.ne == 0) the mark walk looks up no hop's replay-CSR
+// entry; the time pass needs it for the hop latency of the flows with a hit.
+hipError_t launch_timeline_mark_pairs(const ReplayCSR& g, const PairChains& pc, const TraceIds& ids,
+                                      const TraceReqs& rq, const int32_t* hops,
+                                      const CrossWatch& cw, int64_t* seg, unsigned long long* cnt,
+                                      hipStream_t stream);
+hipError_t launch_timeline_time_pairs(const ReplayCSR& g, const PairChains& pc, const TraceIds& ids,
+                                      const TraceReqs& rq, const unsigned long long* w,
+                                      const unsigned long long* now, const int32_t* hops,
+                                      const CrossWatch& cw, const int64_t* loff, uint2* stage,
+                                      const TimeBins& tb, unsigned long long* cnt,
+                                      hipStream_t stream);
+
 hipError_t launch_pair_table_complete(int A, int64_t row0, int64_t rows, const double* elatAA,
                                       const double* elossAA, const double* vlossA, double2* out_lr,
                                       uint16_t* out_hops, double* out_rowmin,

@@ -519,6 +519,60 @@ class Topology:
             raise RuntimeError("shdtopo_link_crossings_stats failed")
         return {k: getattr(s, k) for k, _ in L.ShdCrossStats._fields_}
 
+    # ---- link timeline ----
+    def link_timeline(self, src_ips, dst_ips, now=None, edges=(), vertices=(), weight=None, t0=0,
+                      bin_ns=1_000_000, nbins=0):
+        """shdtopo_link_timeline: the weight of the flows (src, dst, weight) per time bin on the
+        watched edges (``edges``: edge ids) and vertices (``vertices``: vertex ids), along the
+        routes trace_routes reports.  ``now`` is each flow's emission time in ns (None: 0 each,
+        the bins are then time since emission); a hop over a watched edge is timed now + the
+        latency of the route before it, an arrival at a watched vertex now + the latency up to and
+        with the hop.  Bin b covers [t0 + b * bin_ns, t0 + (b + 1) * bin_ns).  Returns a dict:
+        ``hits``, the number of hits in range or not (link_crossings' total); uint64 arrays
+        ``edge_fwd[ne][nbins]`` (hops leaving eu[e]; self loops; every arc of a directed
+        topology), ``edge_rev[ne][nbins]`` and ``vertex[nv][nbins]``; and ``outside``, a dict of
+        the same three keys with [rows][2] arrays: the weight before t0 and at or after the last
+        bin."""
+        s = np.ascontiguousarray(src_ips, dtype=np.uint32)
+        d = np.ascontiguousarray(dst_ips, dtype=np.uint32)
+        if s.shape != d.shape or s.ndim != 1:
+            raise ValueError("src_ips and dst_ips must be 1-D and of one length")
+        n = len(s)
+        w = t = None
+        if weight is not None:
+            w = np.ascontiguousarray(weight, dtype=np.uint64)
+            if w.shape != s.shape:
+                raise ValueError("weight must have one entry per flow")
+        if now is not None:
+            t = np.ascontiguousarray(now, dtype=np.uint64)
+            if t.shape != s.shape:
+                raise ValueError("now must have one entry per flow")
+        we = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1)
+        wv = np.ascontiguousarray(vertices, dtype=np.int32).reshape(-1)
+        ne, nv, nbins = len(we), len(wv), int(nbins)
+        rows = 2 * ne + nv
+        bins = np.zeros((rows, max(nbins, 0)), np.uint64)
+        outside = np.zeros((rows, 2), np.uint64)
+        hits = int(self._lib.shdtopo_link_timeline(
+            self._h, _p(s), _p(d), _p(w) if w is not None else None,
+            _p(t) if t is not None else None, n, _p(we) if ne else None, ne,
+            _p(wv) if nv else None, nv, int(t0), int(bin_ns), nbins,
+            _p(bins) if bins.size else None, _p(outside) if rows else None))
+        if hits < 0:
+            raise RuntimeError("shdtopo_link_timeline failed: %d" % hits)
+        split = lambda x: {"edge_fwd": x[:ne], "edge_rev": x[ne:2 * ne], "vertex": x[2 * ne:]}
+        out = split(bins)
+        out["outside"] = split(outside)
+        out["hits"] = hits
+        return out
+
+    def link_timeline_stats(self):
+        """The last link_timeline's own counters (shdtopo_link_timeline_stats)."""
+        s = L.ShdTimelineStats()
+        if self._lib.shdtopo_link_timeline_stats(self._h, ctypes.byref(s)) != 0:
+            raise RuntimeError("shdtopo_link_timeline_stats failed")
+        return {k: getattr(s, k) for k, _ in L.ShdTimelineStats._fields_}
+
     def write_graphml(self, path):
         if self._lib.shdtopo_write_graphml(self._h, path.encode()) != 0:
             raise RuntimeError("write_graphml failed")
