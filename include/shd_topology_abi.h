@@ -724,6 +724,127 @@ int64_t shdtopo_link_timeline(Topology* top, const uint32_t* srcIP, const uint32
                                                    the last bin}; may be NULL */);
 int shdtopo_link_timeline_stats(Topology* top, ShdTimelineStats* out);
 
+/* ---- link monitor: running per-bin link traffic fed by packet windows ----
+ * shdtopo_link_timeline answers one call: it walks every flow's route and overwrites its outputs.
+ * A link monitor is the same question kept open across a run.  It is a persistent object of its
+ * topology that holds a watch set (edges and vertices, as shdtopo_link_crossings), a bin geometry
+ * (t0, binNs, nbins, as shdtopo_link_timeline), cumulative bins in device memory and a
+ * device-resident hit index over the table's A x A column pairs.
+ *
+ * After any sequence of feeds the monitor's bins and outside pairs equal, byte for byte, what
+ * shdtopo_link_timeline returns for the concatenation of all fed packets that were not filtered
+ * out, with the same watches and bins: rows, hop rules, ns(), the accumulation order of the prefix
+ * latency, self pairs (two hosts on one vertex share a column: a self pair) and the wrapping u64
+ * arithmetic are those of the "link timeline" section above.  Nothing new is modelled.
+ *
+ * For a fixed watch set and attached set, enter_k - now and arrive_k - now of a hit depend on the
+ * (source column, destination column) pair alone.  shdtopo_monitor_prepare walks the routes once
+ * with the timeline's machinery (sources in blocks of one chunk; options "trace_chunk" and
+ * "trace_batch" keep their meaning) and keeps, per pair, its hits {row, offset ns} in hop order,
+ * within a hop the edge record before the vertex record: 16 B a record and one i64 offset per
+ * pair.  A feed then costs one gather and one u64 atomic add per hit per packet.
+ * Complete topologies build the index on the host from the parsed graph (one hop over the direct
+ * edge: offset 0, arrival ns(0.0 + latency); a self pair over its loop); their host feeds use no
+ * device, shdtopo_monitor_feed_device uploads that index once and runs the same kernel.
+ *
+ * Monitors are small integer ids of their topology, not pointers: a stale id (freed) or the id of
+ * another topology's monitor returns -1 from every call and dereferences nothing.
+ * shdtopo_topology_free releases every remaining monitor.
+ *
+ *   shdtopo_monitor_new      id >= 0; -1 on the argument errors shdtopo_link_timeline lists (n and
+ *                            the IP and output arrays aside).  ne + nv == 0 is valid: such a
+ *                            monitor builds no index and every feed returns 0.  Uses no device.
+ *   shdtopo_monitor_prepare  builds or rebuilds the index for the current column geometry (the
+ *                            columns shdtopo_route_batch_device sees, those deferred by
+ *                            shdtopo_window_hold included); returns the number of records.  The
+ *                            feeds call it themselves when the index is missing or stale (the
+ *                            attached set or the geometry moved since it was built).  The bins
+ *                            survive a rebuild: rows are per watch, not per column.  -5: the
+ *                            index does not fit option "monitor_index_mb" (a double, MB; 0, the
+ *                            default: half of the device memory free at prepare) -- found by the
+ *                            count pass, before the records of the block that exceeds it are
+ *                            allocated; the monitor stays unprepared, later feeds return -5 and
+ *                            the bins are untouched.
+ *   shdtopo_monitor_feed     host arrays; the IPs resolve exactly as in shdtopo_link_timeline (a
+ *                            request with an unattached end contributes nothing and is counted).
+ *                            Packets with delivered[i] == 0 are skipped.  Returns this feed's
+ *                            hits, in range or not.  -1: NULL IP array with n > 0, n negative.
+ *   shdtopo_monitor_feed_vertices  the same with original vertex ids (-1 = not attached).
+ *   shdtopo_monitor_feed_device    the arrays of shdtopo_route_batch_device, resident in device
+ *                            memory; enqueued on `stream` (NULL: the library's), not awaited;
+ *                            returns 0 or a negative error.  A column outside [0, A) is skipped
+ *                            and counted (bad_columns), nothing is read through it.  The monitor
+ *                            owns one event: each device feed records it on its stream, a feed
+ *                            on another stream than the previous one first waits on it.
+ *   shdtopo_monitor_read     the cumulative bins, shapes as shdtopo_link_timeline (either may be
+ *                            NULL).
+ *   shdtopo_monitor_reset    zeroes the bins and the cumulative counters; keeps the index.
+ *   shdtopo_monitor_stats    counters and index facts, below.
+ *   shdtopo_monitor_export_index  test hook: pair (s, d) owns records [pairOff[s A + d],
+ *                            pairOff[s A + d + 1]); returns the number of records (prepares if
+ *                            needed); arrays are written when cap >= that (cap = 0 sizes them;
+ *                            any pointer may be NULL).
+ * read, stats, reset, prepare, export_index and free synchronise the monitor's event and the
+ * library's stream first.  The n == 0 feed and the feeds of a monitor without watches launch
+ * nothing.
+ *
+ * Every call takes the build lock.  Like the rest of the family a monitor materialises no lazy
+ * row, pushes no minimum, neither invalidates nor rebuilds the table, and leaves ShdStats and the
+ * trace, load, crossings and timeline statistics as they were.  A multi-device topology monitors
+ * on its first device. */
+typedef struct {
+    double  prepare_ms;          /* wall time of the last prepare */
+    double  replay_ms;           /* of it: event time of the heap-replay launches */
+    double  kernel_ms;           /* of it: event time of everything but replay and keep launches */
+    double  batch_ms;            /* of it: event time of the batch kernel's keep launches */
+    double  feed_kernel_ms;      /* event time of the last feed's kernel (0: none, host walk) */
+    /* cumulative since monitor_new / monitor_reset */
+    int64_t hits, flows_hit, in_range, before, after;
+    int64_t fed;                 /* packets looked up in the index */
+    int64_t skipped_undelivered; /* delivered[i] == 0 */
+    int64_t unattached;          /* host feeds: an end that is no column */
+    int64_t bad_columns;         /* device feeds: a column outside [0, A) */
+    /* the last feed alone */
+    int64_t last_hits, last_flows_hit, last_in_range, last_before, last_after;
+    int64_t last_fed, last_skipped_undelivered, last_unattached, last_bad_columns;
+    int64_t feeds;               /* feed calls since monitor_new */
+    /* the index */
+    int64_t index_pairs;         /* A x A (0: not prepared) */
+    int64_t index_records;
+    int64_t index_bytes;         /* offsets + records */
+    int64_t prepares;            /* index builds since monitor_new */
+    /* the last prepare */
+    int64_t sources;             /* source columns walked */
+    int64_t chunks;              /* source blocks (one chunk each) */
+    int64_t batch_sources;       /* sources answered from the batch kernel's parent records */
+    int64_t batch_fallback;      /* sources that ran a keep launch and then the heap replay */
+    int64_t broken_pairs;        /* unroutable pairs: no records */
+} ShdMonitorStats;
+
+int shdtopo_monitor_new(Topology* top, const int32_t* watchEdge, int64_t ne,
+                        const int32_t* watchVertex, int64_t nv, uint64_t t0, uint64_t binNs,
+                        int64_t nbins);
+int shdtopo_monitor_free(Topology* top, int id);
+int64_t shdtopo_monitor_prepare(Topology* top, int id);
+int64_t shdtopo_monitor_feed(Topology* top, int id, const uint32_t* srcIP, const uint32_t* dstIP,
+                             const uint64_t* weight /* NULL: 1 each */,
+                             const uint64_t* now /* ns; NULL: 0 each */,
+                             const uint8_t* delivered /* NULL: all */, int64_t n);
+int64_t shdtopo_monitor_feed_vertices(Topology* top, int id, const int32_t* srcVertex,
+                                      const int32_t* dstVertex, const uint64_t* weight,
+                                      const uint64_t* now, const uint8_t* delivered, int64_t n);
+int shdtopo_monitor_feed_device(Topology* top, int id, const int32_t* d_srcCol,
+                                const int32_t* d_dstCol,
+                                const uint32_t* d_payload /* weight; NULL: 1 each */,
+                                const uint64_t* d_now /* NULL: 0 each */,
+                                const uint8_t* d_delivered /* NULL: all */, int64_t n,
+                                void* stream);
+int shdtopo_monitor_read(Topology* top, int id, uint64_t* bins, uint64_t* outside);
+int shdtopo_monitor_reset(Topology* top, int id);
+int shdtopo_monitor_stats(Topology* top, int id, ShdMonitorStats* out);
+int64_t shdtopo_monitor_export_index(Topology* top, int id, int64_t* pairOff /* A*A + 1 */,
+                                     int32_t* row, uint64_t* offNs, int64_t cap);
+
 /* Test hook: the device graph preparation (topo_prep.hip) read back -- perm
  * int32[V] (relabelled -> original vertex), rowptr u32[V+1], the adjacency columns u32[2E']
  * (relabelled ids, rows ascending by neighbour), pi f64[V] (= d(h0, .), relabelled ids) and the

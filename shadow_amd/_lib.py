@@ -102,6 +102,19 @@ class ShdTimelineStats(ctypes.Structure):
                 ("before", i64), ("after", i64), ("staged_hops", i64)]
 
 
+class ShdMonitorStats(ctypes.Structure):
+    _fields_ = [("prepare_ms", dbl), ("replay_ms", dbl), ("kernel_ms", dbl), ("batch_ms", dbl),
+                ("feed_kernel_ms", dbl), ("hits", i64), ("flows_hit", i64), ("in_range", i64),
+                ("before", i64), ("after", i64), ("fed", i64), ("skipped_undelivered", i64),
+                ("unattached", i64), ("bad_columns", i64), ("last_hits", i64),
+                ("last_flows_hit", i64), ("last_in_range", i64), ("last_before", i64),
+                ("last_after", i64), ("last_fed", i64), ("last_skipped_undelivered", i64),
+                ("last_unattached", i64), ("last_bad_columns", i64), ("feeds", i64),
+                ("index_pairs", i64), ("index_records", i64), ("index_bytes", i64),
+                ("prepares", i64), ("sources", i64), ("chunks", i64), ("batch_sources", i64),
+                ("batch_fallback", i64), ("broken_pairs", i64)]
+
+
 class ShdSynthParams(ctypes.Structure):
     _fields_ = [("seed", u64), ("n_routers", i64), ("n_poi", i64), ("n_edges", i64),
                 ("integer_latency", ctypes.c_int), ("alpha", dbl), ("directed", ctypes.c_int)]
@@ -162,6 +175,16 @@ SIGNATURES = {
     "shdtopo_link_crossings_stats": (ctypes.c_int, [P, P]),
     "shdtopo_link_timeline": (i64, [P, P, P, P, P, i64, P, i64, P, i64, u64, u64, i64, P, P]),
     "shdtopo_link_timeline_stats": (ctypes.c_int, [P, P]),
+    "shdtopo_monitor_new": (ctypes.c_int, [P, P, i64, P, i64, u64, u64, i64]),
+    "shdtopo_monitor_free": (ctypes.c_int, [P, ctypes.c_int]),
+    "shdtopo_monitor_prepare": (i64, [P, ctypes.c_int]),
+    "shdtopo_monitor_feed": (i64, [P, ctypes.c_int, P, P, P, P, P, i64]),
+    "shdtopo_monitor_feed_vertices": (i64, [P, ctypes.c_int, P, P, P, P, P, i64]),
+    "shdtopo_monitor_feed_device": (ctypes.c_int, [P, ctypes.c_int, P, P, P, P, P, i64, P]),
+    "shdtopo_monitor_read": (ctypes.c_int, [P, ctypes.c_int, P, P]),
+    "shdtopo_monitor_reset": (ctypes.c_int, [P, ctypes.c_int]),
+    "shdtopo_monitor_stats": (ctypes.c_int, [P, ctypes.c_int, P]),
+    "shdtopo_monitor_export_index": (i64, [P, ctypes.c_int, P, P, P, i64]),
     "shdtopo_test_segsort": (ctypes.c_int, [P, i64, P, i64, ctypes.c_int, P, P]),
     "shdtopo_test_batch_layout": (ctypes.c_int, [P, i64, dbl, ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_int, P, P, P]),
@@ -183,6 +206,7 @@ SIGNATURES.update({
     "topowindow_flush": (ctypes.c_int, [P, u64, ctypes.c_int, WINDOW_DELIVER, P]),
     "topowindow_jump_ns": (u64, [P, u64]),
     "topowindow_serial_window_ns": (u64, [P]),
+    "topowindow_set_monitor": (ctypes.c_int, [P, ctypes.c_int, ctypes.c_int]),
 })
 
 SHIM_SIGNATURES = {

@@ -579,6 +579,52 @@ hipError_t launch_timeline_time_pairs(const ReplayCSR& g, const PairChains& pc, 
                                       const TimeBins& tb, unsigned long long* cnt,
                                       hipStream_t stream);
 
+// ---- link monitor (topo_monitor.hip): running per-bin link traffic fed by packet windows ----
+// one hit of a column pair: the row of TimeBins it lands in and ns(prefix latency), the offset the
+// feed adds to a packet's emission time (16 B: one aligned load)
+struct __attribute__((aligned(16))) MonRec {
+    unsigned long long offNs;
+    uint32_t row, pad;
+};
+// The hit index: pair (s, d) of the A x A column pairs owns rec[off[s A + d], off[s A + d + 1]),
+// in hop order, within a hop the edge record before the vertex record; off has A x A + 1 entries.
+struct MonIndex {
+    const int64_t* off = nullptr;
+    const MonRec* rec = nullptr;
+    int64_t nrec = 0;
+    int32_t A = 0;
+};
+// counters of a monitor (u64 words): [0, MN_COUNT) cumulative, [MN_COUNT, 2 MN_COUNT) the last
+// feed's (zeroed by the caller before it); the hits are IN + BEFORE + AFTER
+enum { MN_IN = 0, MN_BEFORE, MN_AFTER, MN_FLOWS, MN_FED, MN_SKIPPED, MN_BAD, MN_COUNT };
+// Fill: the timeline's time pass over the requests of one block of sources, request ridx = the
+// block's pair: instead of binning, the hits' {ns(prefix), row} are stored at rec[goff[ridx]] ..
+// rec[goff[ridx + 1]) (goff: the exclusive scan of launch_cross_count's gcnt); loff / stage as
+// launch_timeline_time (the scan of launch_timeline_mark's seg).
+hipError_t launch_monitor_fill(const ReplayCSR& g, const ReplayWs& ws, const TraceIds& ids,
+                               const TraceReqs& rq, const int32_t* hops, const CrossWatch& cw,
+                               const int64_t* loff, uint2* stage, const int64_t* goff, MonRec* rec,
+                               hipStream_t stream);
+hipError_t launch_monitor_fill_pairs(const ReplayCSR& g, const PairChains& pc, const TraceIds& ids,
+                                     const TraceReqs& rq, const int32_t* hops,
+                                     const CrossWatch& cw, const int64_t* loff, uint2* stage,
+                                     const int64_t* goff, MonRec* rec, hipStream_t stream);
+// out[i] = in[i] + base for i < n
+hipError_t launch_monitor_offsets(const int64_t* in, int64_t* out, int64_t n, int64_t base,
+                                  hipStream_t stream);
+// Feed: packet k (skipped when delivered[k] == 0; counted MN_BAD, nothing read through it, when a
+// column is outside [0, A)) adds its weight (payload[k], NULL: 1) for every record of its pair to
+// the bin of now[k] + offNs (NULL: 0), by TimelineOut::add's rule.  Enqueued, not awaited.
+hipError_t launch_monitor_feed(int64_t n, const int32_t* src, const int32_t* dst,
+                               const uint32_t* payload, const unsigned long long* now,
+                               const uint8_t* delivered, const MonIndex& ix, const TimeBins& tb,
+                               unsigned long long* cnt, hipStream_t stream);
+// the same with u64 weights (the host feeds)
+hipError_t launch_monitor_feed_u64(int64_t n, const int32_t* src, const int32_t* dst,
+                                   const unsigned long long* weight, const unsigned long long* now,
+                                   const uint8_t* delivered, const MonIndex& ix, const TimeBins& tb,
+                                   unsigned long long* cnt, hipStream_t stream);
+
 hipError_t launch_pair_table_complete(int A, int64_t row0, int64_t rows, const double* elatAA,
                                       const double* elossAA, const double* vlossA, double2* out_lr,
                                       uint16_t* out_hops, double* out_rowmin,

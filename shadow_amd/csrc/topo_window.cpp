@@ -3,6 +3,8 @@
 // as one GPU batch at the scheduler's window barrier (shd-slave.c:415-461).
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -12,6 +14,10 @@
 extern "C" {
 __attribute__((weak)) uint32_t address_toNetworkIP(Address* address);
 __attribute__((weak)) double random_nextDouble(Random* random);
+// src/support/shd-logging.h:122-124, as topo_core.cpp imports it
+__attribute__((weak)) void logging_log(const char* log_domain, int log_level, const char* fileName,
+                                       const char* functionName, int lineNumber,
+                                       const char* format, ...);
 }
 
 // One recorded packet: its vertices are resolved at emit, when the reference routed it
@@ -28,6 +34,8 @@ struct _TopoWindow {
     std::mutex mu;  // worker threads emit concurrently; the window keeps their real-time order
     std::vector<WinPacket> in;
     std::vector<TopoPacketOut> out;
+    int monitor = -1;         // topowindow_set_monitor: the link monitor fed at every flush
+    bool monitorBytes = true;  // its weight: payloadLength, else 1 per packet
 };
 
 extern "C" {
@@ -79,6 +87,14 @@ int64_t topowindow_pending(TopoWindow* w) {
     return (int64_t)w->in.size();
 }
 
+int topowindow_set_monitor(TopoWindow* w, int monitor, int bytes) {
+    if (!w) return -1;
+    std::lock_guard<std::mutex> lk(w->mu);
+    w->monitor = monitor < 0 ? -1 : monitor;
+    w->monitorBytes = bytes != 0;
+    return 0;
+}
+
 int topowindow_flush(TopoWindow* w, uint64_t jumpNs, int multiThreaded, TopoWindowDeliver deliver,
                      void* ctx) {
     if (!w) return -1;
@@ -115,6 +131,34 @@ int topowindow_flush(TopoWindow* w, uint64_t jumpNs, int multiThreaded, TopoWind
         in.insert(in.end(), w->in.begin(), w->in.end());
         w->in.swap(in);
         return r;
+    }
+    // the link monitor sees the window before its deferred columns go: the packets the batch
+    // delivered, at their emission times.  A feed error costs the monitor the window, not the run.
+    int monitor;
+    bool bytes;
+    {
+        std::lock_guard<std::mutex> lk(w->mu);
+        monitor = w->monitor;
+        bytes = w->monitorBytes;
+    }
+    if (monitor >= 0) {
+        std::vector<uint64_t> wt;
+        std::vector<uint8_t> dl(n);
+        if (bytes) wt.assign(pay.begin(), pay.end());
+        for (size_t i = 0; i < n; i++) dl[i] = w->out[i].delivered ? 1 : 0;
+        const int64_t fr = shdtopo_monitor_feed_vertices(w->top, monitor, sv.data(), dv.data(),
+                                                         bytes ? wt.data() : nullptr, now.data(),
+                                                         dl.data(), (int64_t)n);
+        if (fr < 0) {
+            if (logging_log)
+                logging_log("shadow", 1 << 4, __FILE__, __FUNCTION__, __LINE__,
+                            "link monitor %d: feeding a window of %lld packets failed: %lld",
+                            monitor, (long long)n, (long long)fr);
+            else if (!getenv("SHDTOPO_LOG") || atoi(getenv("SHDTOPO_LOG")) >= 1)
+                fprintf(stderr,
+                        "[shdtopo] warning: link monitor %d: feeding a window of %lld packets "
+                        "failed: %lld\n", monitor, (long long)n, (long long)fr);
+        }
     }
     // the window's packets are routed: vertices detached during it may leave the table now
     shdtopo_window_release(w->top);

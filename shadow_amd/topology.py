@@ -573,6 +573,13 @@ class Topology:
             raise RuntimeError("shdtopo_link_timeline_stats failed")
         return {k: getattr(s, k) for k, _ in L.ShdTimelineStats._fields_}
 
+    # ---- link monitor ----
+    def link_monitor(self, edges=(), vertices=(), t0=0, bin_ns=1_000_000, nbins=0):
+        """shdtopo_monitor_new: a LinkMonitor of this topology -- link_timeline's watches and bins
+        kept across calls and fed by packet windows (host arrays or the device arrays of
+        route_batch_device) without walking a route."""
+        return LinkMonitor(self, edges, vertices, t0, bin_ns, nbins)
+
     def write_graphml(self, path):
         if self._lib.shdtopo_write_graphml(self._h, path.encode()) != 0:
             raise RuntimeError("write_graphml failed")
@@ -654,6 +661,114 @@ class Topology:
         if r != 0:
             raise RuntimeError("shdtopo_synth_packets failed: %d" % r)
         return out
+
+
+class LinkMonitor:
+    """A link monitor (include/shd_topology_abi.h, "link monitor"): after any sequence of feeds,
+    ``read()`` is what ``Topology.link_timeline`` returns for all fed packets at once."""
+
+    def __init__(self, topology, edges=(), vertices=(), t0=0, bin_ns=1_000_000, nbins=0):
+        self._top = topology
+        self._lib = topology._lib
+        we = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1)
+        wv = np.ascontiguousarray(vertices, dtype=np.int32).reshape(-1)
+        self.ne, self.nv, self.nbins = len(we), len(wv), int(nbins)
+        self.id = int(self._lib.shdtopo_monitor_new(
+            topology._h, _p(we) if self.ne else None, self.ne, _p(wv) if self.nv else None,
+            self.nv, int(t0), int(bin_ns), self.nbins))
+        if self.id < 0:
+            raise RuntimeError("shdtopo_monitor_new failed: %d" % self.id)
+
+    def _check(self, r, what):
+        if r < 0:
+            raise RuntimeError("shdtopo_monitor_%s failed: %d" % (what, r))
+        return r
+
+    def prepare(self):
+        """Build (or rebuild) the hit index for the current columns; the number of records."""
+        return self._check(int(self._lib.shdtopo_monitor_prepare(self._top._h, self.id)),
+                           "prepare")
+
+    def _feed(self, fn, what, a, b, dtype, now, weight, delivered):
+        s = np.ascontiguousarray(a, dtype=dtype)
+        d = np.ascontiguousarray(b, dtype=dtype)
+        if s.shape != d.shape or s.ndim != 1:
+            raise ValueError("the two ends must be 1-D and of one length")
+        opt = []
+        for x, t, name in ((weight, np.uint64, "weight"), (now, np.uint64, "now"),
+                           (delivered, np.uint8, "delivered")):
+            if x is not None:
+                x = np.ascontiguousarray(x, dtype=t)
+                if x.shape != s.shape:
+                    raise ValueError("%s must have one entry per packet" % name)
+            opt.append(x)
+        w, t, dl = opt
+        return self._check(int(fn(self._top._h, self.id, _p(s), _p(d),
+                                  _p(w) if w is not None else None,
+                                  _p(t) if t is not None else None,
+                                  _p(dl) if dl is not None else None, len(s))), what)
+
+    def feed(self, src_ips, dst_ips, now=None, weight=None, delivered=None):
+        """Feed packets given by host IPs (numpy / sequences); this feed's hits."""
+        return self._feed(self._lib.shdtopo_monitor_feed, "feed", src_ips, dst_ips, np.uint32,
+                          now, weight, delivered)
+
+    def feed_vertices(self, src_v, dst_v, now=None, weight=None, delivered=None):
+        """The same by original vertex ids (-1: not attached)."""
+        return self._feed(self._lib.shdtopo_monitor_feed_vertices, "feed_vertices", src_v, dst_v,
+                          np.int32, now, weight, delivered)
+
+    def feed_device(self, src_col, dst_col, now, payload=None, delivered=None, stream=0):
+        """Feed the device arrays of route_batch_device (torch tensors used as plain HBM buffers:
+        int32 columns, uint64-sized now, uint32-sized payload, uint8 delivered).  Enqueued on
+        ``stream``, not awaited."""
+        ptr = lambda x: x.data_ptr() if x is not None else None
+        self._check(int(self._lib.shdtopo_monitor_feed_device(
+            self._top._h, self.id, src_col.data_ptr(), dst_col.data_ptr(), ptr(payload), ptr(now),
+            ptr(delivered), int(src_col.numel()), stream or None)), "feed_device")
+
+    def read(self):
+        """The cumulative bins: the dict link_timeline returns (``hits``: the cumulative hits)."""
+        ne, nv, nbins = self.ne, self.nv, self.nbins
+        rows = 2 * ne + nv
+        bins = np.zeros((rows, max(nbins, 0)), np.uint64)
+        outside = np.zeros((rows, 2), np.uint64)
+        self._check(int(self._lib.shdtopo_monitor_read(
+            self._top._h, self.id, _p(bins) if bins.size else None,
+            _p(outside) if rows else None)), "read")
+        split = lambda x: {"edge_fwd": x[:ne], "edge_rev": x[ne:2 * ne], "vertex": x[2 * ne:]}
+        out = split(bins)
+        out["outside"] = split(outside)
+        out["hits"] = self.stats()["hits"]
+        return out
+
+    def reset(self):
+        self._check(int(self._lib.shdtopo_monitor_reset(self._top._h, self.id)), "reset")
+
+    def stats(self):
+        s = L.ShdMonitorStats()
+        self._check(int(self._lib.shdtopo_monitor_stats(self._top._h, self.id, ctypes.byref(s))),
+                    "stats")
+        return {k: getattr(s, k) for k, _ in L.ShdMonitorStats._fields_}
+
+    def export_index(self):
+        """Test hook: ``(pair_off int64[A*A + 1], row int32[R], off_ns uint64[R])`` -- pair
+        (s, d) owns records [pair_off[s*A + d], pair_off[s*A + d + 1]) in hop order."""
+        n = self._check(int(self._lib.shdtopo_monitor_export_index(
+            self._top._h, self.id, None, None, None, 0)), "export_index")
+        pairs = self.stats()["index_pairs"]
+        off = np.zeros(pairs + 1, np.int64)
+        row = np.zeros(max(n, 1), np.int32)
+        ns = np.zeros(max(n, 1), np.uint64)
+        if pairs:
+            self._check(int(self._lib.shdtopo_monitor_export_index(
+                self._top._h, self.id, _p(off), _p(row), _p(ns), n)), "export_index")
+        return off, row[:n], ns[:n]
+
+    def free(self):
+        if self.id >= 0:
+            self._lib.shdtopo_monitor_free(self._top._h, self.id)
+            self.id = -1
 
 
 def shim():
