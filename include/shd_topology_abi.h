@@ -845,6 +845,107 @@ int shdtopo_monitor_stats(Topology* top, int id, ShdMonitorStats* out);
 int64_t shdtopo_monitor_export_index(Topology* top, int id, int64_t* pairOff /* A*A + 1 */,
                                      int32_t* row, uint64_t* offNs, int64_t cap);
 
+/* ---- link failure what-if: derived topologies and a device-side table diff ----
+ * The trace, the load, the crossings, the timeline and the monitor describe traffic on the network
+ * as it is.  These calls fail links and routers: shdtopo_derive_without makes a second topology
+ * without them, carrying the same hosts on the same vertices, and shdtopo_table_diff compares the
+ * two routing tables on the device and returns only the pairs that changed.  A full table builds
+ * fast enough that recomputing everything after a failure is cheaper than any incremental scheme
+ * walking routes, so nothing here is incremental.
+ *
+ * shdtopo_derive_without returns a new, independent, ordinary Topology (free it with
+ * topology_free; the parent may be freed first).  The parent is read under its locks and otherwise
+ * left exactly as it was.
+ *
+ * The derived graph.  A failed edge is removed; a failed vertex loses all its incident edges, its
+ * self loop included, and stays behind as an isolated vertex.  Edge ids are the parent's edge ids
+ * with the removed ones squeezed out, order kept -- igraph's "lowest edge id" rule and its
+ * incidence order are then those of deleting the edges in igraph, ties included.  Vertex ids and
+ * all vertex attributes are unchanged.  Nothing is parsed or written: the graph is filtered from
+ * the parent's in memory and then goes through the same validation and background preparation as
+ * a graph from topology_new.  Every other entry point works on a derived topology unchanged.
+ *
+ * Validation.  Duplicate ids in the failing lists are allowed.  An empty failing set is valid: a
+ * copy whose table is bit-identical to the parent's.  On an error the call returns NULL, *err (may
+ * be NULL) receives the code, and no device is initialised:
+ *   -1  NULL top; a negative count; a NULL array with a positive count; an edge id outside
+ *       [0, E) or a vertex id outside [0, V);
+ *   -2  a failed vertex has a host attached in the parent;
+ *   -3  the vertices that are not failed do not remain strongly connected (the reference refuses
+ *       any other graph; failed vertices are exempt).  A critical log line names the number of
+ *       vertices cut off: those outside the largest strongly connected part found.
+ * Partitioned networks are out of scope: a failing set that splits the network is refused, not
+ * modelled.
+ *
+ * What is carried over.  Every IP attached in the parent is attached to the same vertex, several
+ * hosts on one vertex included, with no random draw: shdtopo_attached_vertices is equal on both
+ * and columns mean the same thing.  Columns a window adapter has only deferred are not carried;
+ * neither are monitors, windows, lazy rows, statistics or the table.  A failed vertex (of this
+ * derivation or of an earlier one) is never an attachment candidate of the derived topology; later
+ * topology_attach calls otherwise follow the reference's algorithm and RNG use over the derived
+ * graph.  The device ordinal, "abort_on_error" and "lazy" are inherited; every other option
+ * starts at its default.
+ *
+ * shdtopo_edge_origin writes, for each edge id of top, the id of that edge in the root topology
+ * (the one that was loaded or synthesised); a derived topology of a derived topology composes the
+ * maps, a root topology gives the identity.  Returns E (-1: NULL top) and writes only when
+ * cap >= E. */
+Topology* shdtopo_derive_without(Topology* top, const int32_t* failEdge, int64_t ne,
+                                 const int32_t* failVertex, int64_t nv,
+                                 int32_t* err /* may be NULL */);
+int64_t shdtopo_edge_origin(Topology* top, int32_t* origin, int64_t cap);
+
+/* shdtopo_table_diff compares the device-resident A x A tables of a and b pair by pair: the
+ * {latency, reliability} records and the u16 hops.  Latency and reliability are compared bit for
+ * bit as u64, hops as integers; a pair is changed when any of the three differs.  kind bits:
+ *   1  latency rose (lat1 > lat0)
+ *   2  latency fell (lat1 < lat0; possible because any two topologies with the same attached
+ *      vertices are accepted, not only parent and child)
+ *   4  reliability bits differ
+ *   8  hops differ
+ * a's values are lat0 / rel0 / hops0, b's lat1 / rel1 / hops1.  Records come out in row-major
+ * order, by srcCol then dstCol: deterministic.  Returns the total number of changed pairs; out
+ * receives the first min(total, cap) records of that order (cap = 0 with out = NULL sizes the
+ * buffer).  kindCount[i] = pairs with bit 1 << i set; rowChanged[s] = changed pairs of row s;
+ * rowWorstRise[s] = the largest lat1 - lat0 (one f64 subtraction) over the pairs of row s whose
+ * latency rose, rowWorstCol[s] the lowest column reaching it; 0.0 and -1 when no latency of the
+ * row rises.  The three row arrays have A entries.  Any output pointer may be NULL.
+ *
+ * A topology without a valid table gets it built, as by shdtopo_build.  The call then takes both
+ * build locks in a fixed order (by address).  Negative on an error: -1 NULL topology, negative
+ * cap, or NULL out with cap > 0; -4 the attached vertex lists are not identical; -6 the two tables
+ * live on different devices; -5 the attached sets kept changing under the call.  a == b is valid
+ * and returns 0.
+ *
+ * Device work (topo_diff.hip): a count pass over the pairs, the exclusive scan of the row counts,
+ * a fill pass that writes each row's records at its offset in column order (wave ballots and
+ * prefix popcounts, no sort); 36 B are read per pair and pass, the fill pass skips rows without a
+ * change and rows past cap.  Only the changed records and the per-row arrays leave the device.
+ * Like the rest of the family the call materialises no lazy row, pushes no minimum, and leaves
+ * ShdStats and the trace, load, crossings and timeline statistics as they were (a table it had to
+ * build is a build like any other).  shdtopo_table_diff_stats reads the statistics of the last
+ * diff in which `a` was the first argument. */
+typedef struct {
+    int32_t  srcCol, dstCol;
+    double   lat0, lat1, rel0, rel1;
+    uint16_t hops0, hops1;
+    uint32_t kind;
+} ShdTableChange;
+
+typedef struct {
+    double  total_ms;    /* wall time of the call (table builds it had to wait for included) */
+    double  kernel_ms;   /* event time of count, scan and fill */
+    int64_t pairs;       /* A x A */
+    int64_t changed;     /* the call's return value */
+    int64_t bytes_read;  /* table bytes the two passes read: 36 per pair of the count pass and of
+                            every row the fill pass walked */
+} ShdDiffStats;
+
+int64_t shdtopo_table_diff(Topology* a, Topology* b, ShdTableChange* out, int64_t cap,
+                           uint64_t kindCount[4], uint32_t* rowChanged /* [A] */,
+                           double* rowWorstRise /* [A] */, int32_t* rowWorstCol /* [A] */);
+int shdtopo_table_diff_stats(Topology* a, ShdDiffStats* out);
+
 /* Test hook: the device graph preparation (topo_prep.hip) read back -- perm
  * int32[V] (relabelled -> original vertex), rowptr u32[V+1], the adjacency columns u32[2E']
  * (relabelled ids, rows ascending by neighbour), pi f64[V] (= d(h0, .), relabelled ids) and the

@@ -115,6 +115,17 @@ class ShdMonitorStats(ctypes.Structure):
                 ("batch_fallback", i64), ("broken_pairs", i64)]
 
 
+class ShdTableChange(ctypes.Structure):
+    _fields_ = [("srcCol", i32), ("dstCol", i32), ("lat0", dbl), ("lat1", dbl), ("rel0", dbl),
+                ("rel1", dbl), ("hops0", ctypes.c_uint16), ("hops1", ctypes.c_uint16),
+                ("kind", u32)]
+
+
+class ShdDiffStats(ctypes.Structure):
+    _fields_ = [("total_ms", dbl), ("kernel_ms", dbl), ("pairs", i64), ("changed", i64),
+                ("bytes_read", i64)]
+
+
 class ShdSynthParams(ctypes.Structure):
     _fields_ = [("seed", u64), ("n_routers", i64), ("n_poi", i64), ("n_edges", i64),
                 ("integer_latency", ctypes.c_int), ("alpha", dbl), ("directed", ctypes.c_int)]
@@ -185,6 +196,10 @@ SIGNATURES = {
     "shdtopo_monitor_reset": (ctypes.c_int, [P, ctypes.c_int]),
     "shdtopo_monitor_stats": (ctypes.c_int, [P, ctypes.c_int, P]),
     "shdtopo_monitor_export_index": (i64, [P, ctypes.c_int, P, P, P, i64]),
+    "shdtopo_derive_without": (P, [P, P, i64, P, i64, P]),
+    "shdtopo_edge_origin": (i64, [P, P, i64]),
+    "shdtopo_table_diff": (i64, [P, P, P, i64, P, P, P, P]),
+    "shdtopo_table_diff_stats": (ctypes.c_int, [P, P]),
     "shdtopo_test_segsort": (ctypes.c_int, [P, i64, P, i64, ctypes.c_int, P, P]),
     "shdtopo_test_batch_layout": (ctypes.c_int, [P, i64, dbl, ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_int, P, P, P]),

@@ -625,6 +625,34 @@ hipError_t launch_monitor_feed_u64(int64_t n, const int32_t* src, const int32_t*
                                    const uint8_t* delivered, const MonIndex& ix, const TimeBins& tb,
                                    unsigned long long* cnt, hipStream_t stream);
 
+// ---- table diff (topo_diff.hip): the changed pairs of two A x A tables ----
+// one changed pair: the device image of ShdTableChange (include/shd_topology_abi.h); hops =
+// hops0 | hops1 << 16
+struct __attribute__((aligned(16))) DiffRec {
+    int32_t srcCol, dstCol;
+    double lat0, lat1, rel0, rel1;
+    uint32_t hops, kind;
+};
+enum : uint32_t { kDiffLatRose = 1, kDiffLatFell = 2, kDiffRel = 4, kDiffHops = 8 };
+// the two tables of one call, row-major A x A, on the current device
+struct DiffTables {
+    const double2* lr0 = nullptr;
+    const double2* lr1 = nullptr;
+    const uint16_t* hops0 = nullptr;
+    const uint16_t* hops1 = nullptr;
+    int32_t A = 0;
+};
+// Count: one workgroup per row s: rowChanged[s] = its changed pairs, rowWorstRise[s] /
+// rowWorstCol[s] = its largest lat1 - lat0 and the lowest column reaching it (0.0 / -1 when no
+// latency rises), kindCount[i] += its pairs with kind bit 1 << i (u64[4], zeroed by the caller).
+hipError_t launch_diff_count(const DiffTables& t, int64_t* rowChanged, double* rowWorstRise,
+                             int32_t* rowWorstCol, unsigned long long* kindCount,
+                             hipStream_t stream);
+// Fill: row s writes its changed pairs' records, columns ascending, at out[rowOff[s]] .. (rowOff:
+// the exclusive scan of rowChanged); records at or past cap are not written.
+hipError_t launch_diff_fill(const DiffTables& t, const int64_t* rowChanged, const int64_t* rowOff,
+                            DiffRec* out, int64_t cap, hipStream_t stream);
+
 hipError_t launch_pair_table_complete(int A, int64_t row0, int64_t rows, const double* elatAA,
                                       const double* elossAA, const double* vlossA, double2* out_lr,
                                       uint16_t* out_hops, double* out_rowmin,

@@ -860,7 +860,123 @@ bool synth_graph(const SynthParams& p, HostGraph& g, std::string& err) {
     return true;
 }
 
-void AttachIndex::build(const HostGraph& g) {
+// ---------------------------------------------------------------------------------------------
+// link failure what-if (shdtopo_derive_without): connectivity of what remains, the filtered copy
+// ---------------------------------------------------------------------------------------------
+int64_t cut_off_vertices(const HostGraph& g, const std::vector<uint8_t>& dropEdge,
+                         const std::vector<uint8_t>& dropVertex) {
+    const size_t V = (size_t)g.V;
+    int64_t remain = 0;
+    for (size_t v = 0; v < V; v++) remain += dropVertex[v] ? 0 : 1;
+    if (remain == 0) return -1;
+    // out- and in-rows of the surviving edges (undirected: both ends in the out-rows)
+    const bool dir = g.directed;
+    std::vector<int64_t> optr(V + 1, 0), iptr(dir ? V + 1 : 1, 0);
+    auto alive = [&](int64_t e) {
+        return !dropEdge[(size_t)e] && !dropVertex[(size_t)g.eu[(size_t)e]] &&
+               !dropVertex[(size_t)g.ev[(size_t)e]];
+    };
+    for (int64_t e = 0; e < g.E; e++) {
+        if (!alive(e)) continue;
+        const size_t a = (size_t)g.eu[(size_t)e], b = (size_t)g.ev[(size_t)e];
+        optr[a + 1]++;
+        if (dir) iptr[b + 1]++;
+        else optr[b + 1]++;
+    }
+    for (size_t v = 0; v < V; v++) {
+        optr[v + 1] += optr[v];
+        if (dir) iptr[v + 1] += iptr[v];
+    }
+    std::vector<int32_t> oadj((size_t)optr[V]), iadj(dir ? (size_t)iptr[V] : 0);
+    {
+        std::vector<int64_t> po(optr.begin(), optr.end() - 1), pi(iptr.begin(), iptr.end() - 1);
+        for (int64_t e = 0; e < g.E; e++) {
+            if (!alive(e)) continue;
+            const int32_t a = g.eu[(size_t)e], b = g.ev[(size_t)e];
+            oadj[(size_t)po[(size_t)a]++] = b;
+            if (dir) iadj[(size_t)pi[(size_t)b]++] = a;
+            else oadj[(size_t)po[(size_t)b]++] = a;
+        }
+    }
+    // the strongly connected part of a root = what it reaches and is reached from; roots are
+    // tried in vertex order until one part holds at least half of what remains (no larger one
+    // can exist) or a few have been tried
+    std::vector<uint8_t> mark(V, 0);  // bit 0: forward, bit 1: backward (of the current root)
+    std::vector<uint8_t> placed(V, 0);
+    std::vector<int32_t> st, touched;
+    int64_t best = 0;
+    size_t next = 0;
+    for (int tries = 0; tries < 16 && 2 * best < remain; tries++) {
+        while (next < V && (dropVertex[next] || placed[next])) next++;
+        if (next == V) break;
+        const int32_t root = (int32_t)next;
+        auto sweep = [&](const std::vector<int64_t>& ptr, const std::vector<int32_t>& adj,
+                         uint8_t bit) {
+            st.assign(1, root);
+            if (!mark[(size_t)root]) touched.push_back(root);
+            mark[(size_t)root] |= bit;
+            while (!st.empty()) {
+                const int32_t x = st.back();
+                st.pop_back();
+                for (int64_t i = ptr[(size_t)x]; i < ptr[(size_t)x + 1]; i++) {
+                    const int32_t y = adj[(size_t)i];
+                    if (mark[(size_t)y] & bit) continue;
+                    if (!mark[(size_t)y]) touched.push_back(y);
+                    mark[(size_t)y] |= bit;
+                    st.push_back(y);
+                }
+            }
+        };
+        touched.clear();
+        sweep(optr, oadj, 1);
+        if (dir) sweep(iptr, iadj, 2);
+        const uint8_t full = dir ? 3 : 1;
+        int64_t size = 0;
+        for (int32_t v : touched) {
+            if (mark[(size_t)v] == full) {
+                placed[(size_t)v] = 1;
+                size++;
+            }
+            mark[(size_t)v] = 0;
+        }
+        best = std::max(best, size);
+    }
+    return remain - best;
+}
+
+void derive_graph(const HostGraph& g, const std::vector<uint8_t>& dropEdge, HostGraph& out,
+                  std::vector<int32_t>& origin) {
+    out.V = g.V;
+    out.directed = g.directed;
+    out.vid = g.vid;
+    out.vtype = g.vtype;
+    out.vip = g.vip;
+    out.vgeo = g.vgeo;
+    out.vbwup = g.vbwup;
+    out.vbwdown = g.vbwdown;
+    out.vloss = g.vloss;
+    int64_t keep = 0;
+    for (int64_t e = 0; e < g.E; e++) keep += dropEdge[(size_t)e] ? 0 : 1;
+    out.eu.reserve((size_t)keep);
+    out.ev.reserve((size_t)keep);
+    out.elat.reserve((size_t)keep);
+    out.eloss.reserve((size_t)keep);
+    out.ejitter.reserve((size_t)keep);
+    origin.clear();
+    origin.reserve((size_t)keep);
+    for (int64_t e = 0; e < g.E; e++) {
+        if (dropEdge[(size_t)e]) continue;
+        out.eu.push_back(g.eu[(size_t)e]);
+        out.ev.push_back(g.ev[(size_t)e]);
+        out.elat.push_back(g.elat[(size_t)e]);
+        out.eloss.push_back(g.eloss[(size_t)e]);
+        out.ejitter.push_back((size_t)e < g.ejitter.size() ? g.ejitter[(size_t)e] : 0.0);
+        origin.push_back((int32_t)e);
+    }
+    out.E = keep;
+}
+
+void AttachIndex::build(const HostGraph& g, const std::vector<uint8_t>* exclude) {
     all.clear(); byType.clear(); byCode.clear(); byTypeCode.clear(); byIP.clear();
     ip.assign((size_t)g.V, 0xFFFFFFFFu);
     usable.assign((size_t)g.V, 0);
@@ -871,6 +987,7 @@ void AttachIndex::build(const HostGraph& g) {
     };
     for (int32_t v = 0; v < g.V; v++) {
         if (g.vid[(size_t)v].find("poi") == std::string::npos) continue;  // shd-topology.c:974
+        if (exclude && (*exclude)[(size_t)v]) continue;  // a failed vertex of a derived topology
         uint32_t a = string_to_ip(g.vip[(size_t)v].c_str());
         ip[(size_t)v] = a;
         usable[(size_t)v] = (a != 0xFFFFFFFFu && a != 0u);

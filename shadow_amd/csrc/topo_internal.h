@@ -58,6 +58,16 @@ bool graphml_parse(const char* buf, size_t len, HostGraph& g, std::string& err);
 bool graphml_load_file(const char* path, HostGraph& g, std::string& err);
 bool graphml_write_file(const HostGraph& g, const char* path);
 
+// Link failure what-if (shdtopo_derive_without).  cut_off_vertices: with the edges of dropEdge
+// and the vertices of dropVertex (per edge / per vertex flags) taken out of g, the number of
+// remaining vertices outside the largest strongly connected part found (0: the rest is strongly
+// connected; -1: no vertex remains).  derive_graph: the filtered copy (edge order kept, vertices
+// and their attributes unchanged); origin[e'] = the parent's id of the copy's edge e'.
+int64_t cut_off_vertices(const HostGraph& g, const std::vector<uint8_t>& dropEdge,
+                         const std::vector<uint8_t>& dropVertex);
+void derive_graph(const HostGraph& g, const std::vector<uint8_t>& dropEdge, HostGraph& out,
+                  std::vector<int32_t>& origin);
+
 struct SynthParams {
     uint64_t seed;
     int64_t n_routers, n_poi, n_edges;
@@ -188,7 +198,8 @@ struct AttachIndex {
     std::vector<uint8_t> usable;                                // per vertex
     std::unordered_map<std::string, std::vector<int32_t>> byType, byCode, byTypeCode;
     std::unordered_map<uint32_t, std::vector<int32_t>> byIP;
-    void build(const HostGraph& g);
+    // exclude (per vertex, may be NULL): vertices that are no candidates whatever their id says
+    void build(const HostGraph& g, const std::vector<uint8_t>* exclude = nullptr);
 };
 
 }  // namespace shdtopo

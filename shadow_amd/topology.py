@@ -82,6 +82,12 @@ CROSSING_DTYPE = np.dtype([("flow", np.int32), ("watch", np.int32), ("hop", np.i
                            ("reverse", np.int32)])
 
 
+# one record of Topology.table_diff (ShdTableChange)
+TABLE_CHANGE_DTYPE = np.dtype([("srcCol", np.int32), ("dstCol", np.int32), ("lat0", np.float64),
+                               ("lat1", np.float64), ("rel0", np.float64), ("rel1", np.float64),
+                               ("hops0", np.uint16), ("hops1", np.uint16), ("kind", np.uint32)])
+
+
 def crossings_by_watch(result):
     """Invert a Topology.link_crossings result into {watch index: flow indices} -- every watch of
     the call, the flows ascending, a flow once per record (host side: the records are already in
@@ -579,6 +585,73 @@ class Topology:
         kept across calls and fed by packet windows (host arrays or the device arrays of
         route_batch_device) without walking a route."""
         return LinkMonitor(self, edges, vertices, t0, bin_ns, nbins)
+
+    # ---- link failure what-if ----
+    def without(self, edges=(), vertices=()):
+        """shdtopo_derive_without: a new, independent Topology without the given edges (edge ids)
+        and vertices (vertex ids; they lose every incident edge and stay behind isolated), with
+        every attached host carried over to the same vertex.  Edge ids of the result are this
+        topology's with the removed ones squeezed out (``edge_origin()`` maps them back).  Raises
+        ValueError carrying the error code (``.args[1]``): -1 bad ids, -2 a failed vertex has a
+        host, -3 the rest would not stay strongly connected."""
+        fe = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1)
+        fv = np.ascontiguousarray(vertices, dtype=np.int32).reshape(-1)
+        err = ctypes.c_int32(0)
+        h = self._lib.shdtopo_derive_without(self._h, _p(fe) if len(fe) else None, len(fe),
+                                             _p(fv) if len(fv) else None, len(fv),
+                                             ctypes.byref(err))
+        if not h:
+            raise ValueError("shdtopo_derive_without failed: %d" % err.value, err.value)
+        return Topology(h)
+
+    def edge_origin(self):
+        """shdtopo_edge_origin: per edge id its id in the root topology (the loaded or synthesised
+        one); the identity unless this topology was derived by ``without``."""
+        E = int(self._lib.shdtopo_edge_origin(self._h, None, 0))
+        out = np.empty(max(E, 1), np.int32)
+        self._lib.shdtopo_edge_origin(self._h, _p(out), E)
+        return out[:E]
+
+    def table_diff(self, other, cap=None):
+        """shdtopo_table_diff: the pairs whose {latency, reliability, hops} differ between this
+        topology's table (lat0 / rel0 / hops0) and ``other``'s (lat1 / rel1 / hops1), compared on
+        the device; both must have the same attached vertices.  Returns a dict: ``total``, the
+        number of changed pairs; ``records`` (TABLE_CHANGE_DTYPE), the first min(total, cap) of
+        them ordered by srcCol then dstCol (cap=None sizes the buffer with a cap = 0 call first);
+        ``kind_count`` uint64[4], the pairs with kind bit 1, 2, 4, 8 (latency rose, latency fell,
+        reliability changed, hops changed); per row ``row_changed`` uint32[A], ``row_worst_rise``
+        float64[A] (the largest lat1 - lat0) and ``row_worst_col`` int32[A] (the lowest column
+        reaching it; 0.0 and -1 when no latency of the row rises)."""
+        kind = np.zeros(4, np.uint64)
+
+        def call(out, c, rows):
+            return int(self._lib.shdtopo_table_diff(
+                self._h, other._h, _p(out) if c else None, c, _p(kind),
+                _p(rows[0]) if rows else None, _p(rows[1]) if rows else None,
+                _p(rows[2]) if rows else None))
+        if cap is None:
+            cap = call(None, 0, None)
+            if cap < 0:
+                raise RuntimeError("shdtopo_table_diff failed: %d" % cap, cap)
+        cap = int(cap)
+        A = int(self._lib.shdtopo_num_attached(self._h))
+        rows = (np.zeros(max(A, 1), np.uint32), np.zeros(max(A, 1), np.float64),
+                np.full(max(A, 1), -1, np.int32))
+        records = np.zeros(max(cap, 1), TABLE_CHANGE_DTYPE)
+        total = call(records, cap, rows)
+        if total < 0:
+            raise RuntimeError("shdtopo_table_diff failed: %d" % total, total)
+        return {"total": total, "records": records[:min(total, cap)], "kind_count": kind,
+                "row_changed": rows[0][:A], "row_worst_rise": rows[1][:A],
+                "row_worst_col": rows[2][:A]}
+
+    def table_diff_stats(self):
+        """The last table_diff's own counters, kept by its first topology
+        (shdtopo_table_diff_stats)."""
+        s = L.ShdDiffStats()
+        if self._lib.shdtopo_table_diff_stats(self._h, ctypes.byref(s)) != 0:
+            raise RuntimeError("shdtopo_table_diff_stats failed")
+        return {k: getattr(s, k) for k, _ in L.ShdDiffStats._fields_}
 
     def write_graphml(self, path):
         if self._lib.shdtopo_write_graphml(self._h, path.encode()) != 0:
