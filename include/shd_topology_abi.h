@@ -142,7 +142,10 @@ Topology* shdtopo_new_from_buffer(const char* graphml, size_t len);
  * (shdtopo_trace_routes / shdtopo_link_load: 1, the default, takes a source's routes from the
  * batch kernel's parent records where that is exact and replays only the other sources; 0 always
  * runs the heap replay -- the A/B and test baseline; both give the same bytes; any other value is
- * rejected).
+ * rejected), "h0_seed" (1, the default: the batch kernel's landmark bound d_j(h0) of source j
+ * starts at the graph preparation's d(s_j, h0), scaled up by max(1e-9, 4 V 2^-53), instead of
+ * +inf, so the landmark filter, the target skip and the kappa cut prune from the first expansion;
+ * 0: the bound is learnt from the kernel's tentative value of h0 alone; both give the same table).
  * Returns 0 or -1 for an unknown key / bad value. */
 int shdtopo_set_option(Topology* top, const char* key, double value);
 
@@ -413,6 +416,11 @@ int shdtopo_get_stats(Topology* top, ShdStats* out);
  * when no layout applies (the build then keeps the grouping order).  Host-only: no device use. */
 int shdtopo_test_batch_layout(const double* cost, int64_t rows, double fixed, int fill, int slots,
                               int batch, uint32_t* order, uint32_t* starts, int64_t* nbatches);
+
+/* Test hook: the seed of the batch kernel's landmark bound (option "h0_seed") for a source whose
+ * prepared distance to the landmark is p on a graph of `vertices` vertices: 0 for p = 0, +inf for
+ * a p that is not finite, else p (1 + max(1e-9, 4 vertices 2^-53)) rounded up.  Host-only. */
+double shdtopo_test_h0_seed(double p, int64_t vertices);
 
 /* Test hook: the segmented sort of the target-aware re-sort on HIP device 0 -- nseg rows
  * (rowptr u32[nseg + 1] over n f32 keys) each sorted ascending and stably; keys_out receives the

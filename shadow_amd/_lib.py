@@ -203,6 +203,7 @@ SIGNATURES = {
     "shdtopo_test_segsort": (ctypes.c_int, [P, i64, P, i64, ctypes.c_int, P, P]),
     "shdtopo_test_batch_layout": (ctypes.c_int, [P, i64, dbl, ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_int, P, P, P]),
+    "shdtopo_test_h0_seed": (dbl, [dbl, i64]),
     "shdtopo_export_graph": (ctypes.c_int, [P, P, P, P, P, P]),
     "shdtopo_export_csr": (i64, [P, P, P, P, P, P]),
     "shdtopo_export_prep": (i64, [P, cstr, P, i64]),

@@ -337,6 +337,7 @@ struct _Topology {
     std::vector<int32_t> aaCols;  // the columns the resident A x A edge matrices were built for
     DevBuf<uint32_t> d_sources, d_targets;
     DevBuf<double> d_srcsh;
+    DevBuf<double> d_h0seed;  // per layout position: the landmark bound's seed (source_h0_seeds)
     DevBuf<uint8_t> d_mask;
     DevBuf<uint32_t> d_hpar;
     DevBuf<unsigned long long> d_stats;
@@ -360,6 +361,7 @@ struct _Topology {
     bool tieProbed = false;
     DevBuf<uint32_t> d_probeSrc;
     DevBuf<double> d_probeSh;
+    DevBuf<double> d_probeSeed;
     int replaySlotsOpt = 0;   // option "replay_slots" (0 = sized from the CUs and free HBM)
     int replayWpc = 20;       // option "replay_wpc": replay wavefronts per CU (LDS and HBM allowing)
     bool rwsInt = false;      // the replay workspace's node block is laid out for u32 keys
@@ -383,6 +385,8 @@ struct _Topology {
                                // from its uplink (undirected topologies; topo_sssp_batch.hip)
     bool adjkLeaf = false;     // d_adjk's target-derived content is that of the effective target
                                // set: (adjkTargets - peeled) + uplinks, peeled vertices dead
+    bool h0Seed = true;        // option "h0_seed": the batch kernel's landmark bound d_j(h0) starts
+                               // at the prepared d(s_j, h0) (h0_seed_of) instead of +inf
     std::vector<uint32_t> leafFor;  // the target set d_tleaf / d_tbitsEff / d_dead belong to
     int64_t leafPeeled = 0;         // ... and its peeled targets
     bool adjkFlagged = false;
@@ -1500,6 +1504,35 @@ std::vector<double> source_shifts(Topology* top, const uint32_t* s, int64_t n, d
     return sh;
 }
 
+// Seed of the batch kernel's landmark bound for a source with p = d(s, h0) of the graph
+// preparation (HostPrep::to_h0) on a V-vertex graph: p (1 + m) rounded up, m = max(1e-9,
+// 4 V 2^-53); +inf when p is not finite (no route to h0: no bound), 0 for p = 0 (s = h0).
+// Why it is an upper bound of the kernel's final d_j(h0): p is the fixpoint of IEEE adds that
+// start at the h0 end, the kernel's value the fixpoint of adds that start at the source end.  For
+// the path P that attains p, with n < V hops and u = 2^-53: every partial sum is within (1 +- u)
+// per add of the exact one, so d_j(h0) <= fwd(P) <= exact(P) (1 + u)^n <= bwd(P) ((1 + u) /
+// (1 - u))^n <= p (1 + 2 n u + O((n u)^2)) <= p (1 + m).  The landmark filter, the target skip, the
+// kappa cut and the sweeps' kappa0 test are all proved for any h >= the final d_j(h0)
+// (topo_sssp_batch.hip), so the seed may stand in for the tentative value from the first
+// expansion on.
+double h0_seed_of(double p, int64_t V) {
+    if (!(p < INFINITY)) return INFINITY;
+    if (!(p > 0.0)) return 0.0;
+    const double m = std::max(1e-9, 4.0 * (double)std::max<int64_t>(V, 1) * 0x1p-53);
+    return std::nextafter(p * (1.0 + m), INFINITY);
+}
+
+// landmark bound seeds of the sources s[0 .. n) (relabelled ids); option h0_seed 0: +inf, the
+// kernel then learns d_j(h0) from its own tentative value alone
+std::vector<double> source_h0_seeds(Topology* top, const uint32_t* s, int64_t n) {
+    std::vector<double> hs((size_t)n, INFINITY);
+    if (!top->h0Seed) return hs;
+    const int64_t V = (int64_t)top->hp->pot.size();  // (a multi-GPU peer shares hp, not the graph)
+    for (int64_t i = 0; i < n; i++)
+        hs[(size_t)i] = h0_seed_of(top->hp->to_h0(s[(size_t)i]), V);
+    return hs;
+}
+
 // LDS plan of a batched launch under the current options (lds_hubs, par_hubs)
 SsspLdsPlan batch_lds_plan(Topology* top, int K) {
     return sssp_batch_lds_plan(
@@ -1524,12 +1557,16 @@ int upload_layout(Topology* top, const std::vector<uint32_t>& src, const std::ve
     HIPCHK(top->d_srcsh.ensure((size_t)rows));
     HIPCHK(hipMemcpyAsync(top->d_srcsh.p, sh.data(), sizeof(double) * (size_t)rows,
                           hipMemcpyHostToDevice, st));
+    const std::vector<double> hs = source_h0_seeds(top, psrc.data(), rows);
+    HIPCHK(top->d_h0seed.ensure((size_t)rows));
+    HIPCHK(hipMemcpyAsync(top->d_h0seed.p, hs.data(), sizeof(double) * (size_t)rows,
+                          hipMemcpyHostToDevice, st));
     if (bstart) {
         HIPCHK(top->d_bstart.ensure(bstart->size()));
         HIPCHK(hipMemcpyAsync(top->d_bstart.p, bstart->data(), 4 * bstart->size(),
                               hipMemcpyHostToDevice, st));
     }
-    HIPCHK(hipStreamSynchronize(st));  // perm / sh / bstart must outlive the copies
+    HIPCHK(hipStreamSynchronize(st));  // perm / sh / hs / bstart must outlive the copies
     return 0;
 }
 
@@ -1938,13 +1975,16 @@ int enqueue_rows(Topology* top, int64_t row0, int64_t row1, double2* out_lr, uin
                     HIPCHK(top->d_probeSh.ensure((size_t)P));
                     HIPCHK(hipMemcpyAsync(top->d_probeSrc.p, src.data(), 4 * (size_t)P, hipMemcpyHostToDevice, st));
                     HIPCHK(hipMemcpyAsync(top->d_probeSh.p, sh.data(), 8 * (size_t)P, hipMemcpyHostToDevice, st));
+                    const std::vector<double> hs = source_h0_seeds(top, src.data(), P);
+                    HIPCHK(top->d_probeSeed.ensure((size_t)P));
+                    HIPCHK(hipMemcpyAsync(top->d_probeSeed.p, hs.data(), 8 * (size_t)P, hipMemcpyHostToDevice, st));
                     SlotWs pws = ws;
                     pws.rowmap = nullptr;  // sample row i -> output row i
                     const SsspLdsPlan bp = batch_lds_plan(top, K);
                     r = hub_rows_ready(top, bp.H, st);
                     if (r) return r;
                     HIPCHK(launch_sssp_batch(K, dev_csr(top), pws, top->d_probeSrc.p, top->d_probeSh.p,
-                                             (int)P, K, top->d_targets.p, (int)A, delta, bp,
+                                             top->d_probeSeed.p, (int)P, K, top->d_targets.p, (int)A, delta, bp,
                                              top->iterGuard, out_lr, out_hops, out_rowmin,
                                              top->d_stats.p, st));
                     std::vector<uint8_t> fl((size_t)P);
@@ -2135,7 +2175,8 @@ int enqueue_rows(Topology* top, int64_t row0, int64_t row1, double2* out_lr, uin
                 if (r) return r;
                 bstep_mark(top, 2);
                 HIPCHK(launch_sssp_batch(K, dev_csr(top), ws, top->d_bsrc.p,
-                                         top->d_srcsh.p, (int)rows, measured ? K : kf, top->d_targets.p,
+                                         top->d_srcsh.p, top->d_h0seed.p, (int)rows,
+                                         measured ? K : kf, top->d_targets.p,
                                          (int)A, delta, bp, top->iterGuard, out_lr, out_hops,
                                          out_rowmin, top->d_stats.p, st));
                 HIPCHK(hipEventRecord(top->ev1, st));
@@ -2431,6 +2472,10 @@ void sync_peer(Topology* top, Topology* p) {
     p->targetKappa = top->targetKappa;
     p->targetResort = top->targetResort;
     p->leafTargets = top->leafTargets;
+    if (p->h0Seed != top->h0Seed) {
+        p->h0Seed = top->h0Seed;
+        p->ordUploaded = false;
+    }
     p->attached = top->attached;
     p->colOf = top->colOf;
     p->A = top->A;
@@ -3508,6 +3553,10 @@ int shdtopo_set_option(Topology* top, const char* key, double value) {
     else if (k == "target_kappa") top->targetKappa = (int)value;
     else if (k == "target_resort") top->targetResort = value != 0;
     else if (k == "leaf_targets") top->leafTargets = value != 0;
+    else if (k == "h0_seed") {
+        top->h0Seed = value != 0;
+        top->ordUploaded = false;  // the uploaded layout carries the seeds
+    }
     else if (k == "exchange") {
         const int m = (int)value;
         if (m < 0 || m > 2) return -1;
@@ -4027,6 +4076,8 @@ int shdtopo_test_batch_layout(const double* cost, int64_t rows, double fixed, in
     return 0;
 }
 
+double shdtopo_test_h0_seed(double p, int64_t vertices) { return h0_seed_of(p, vertices); }
+
 int shdtopo_test_segsort(const uint32_t* rowptr, int64_t nseg, const float* keys, int64_t n,
                          int reference, float* keys_out, uint32_t* idx_out) {
     if (!rowptr || !keys || !keys_out || !idx_out || nseg < 1 || n < 1 || n > 0x7FFFFFFF ||
@@ -4330,7 +4381,7 @@ struct ReplayReqs {
     SlotWs bws;
     PairChains pc;
     DevBuf<uint32_t> d_tgt, d_rmap, d_fsrcs;
-    DevBuf<double> d_srcsh;
+    DevBuf<double> d_srcsh, d_h0seed;
     DevBuf<uint8_t> d_rowflag, d_broken;
     DevBuf<unsigned long long> d_bst;
     // one chunk's chains (chunk_chains): rmap[i] of chunk source i, the sources replayed
@@ -4400,6 +4451,9 @@ int prepare_batch_path(Topology* top, const std::vector<uint32_t>& tgt, bool for
     HIPCHK(R.d_bst.ensure(ST_COUNT));
     HIPCHK(hipMemcpy(R.d_tgt.p, tgt.data(), 4 * (size_t)A, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(R.d_srcsh.p, sh.data(), 8 * (size_t)R.nsrc, hipMemcpyHostToDevice));
+    const std::vector<double> hs = source_h0_seeds(top, R.srcs.data(), R.nsrc);
+    HIPCHK(R.d_h0seed.ensure((size_t)R.nsrc));
+    HIPCHK(hipMemcpy(R.d_h0seed.p, hs.data(), 8 * (size_t)R.nsrc, hipMemcpyHostToDevice));
     if (leaf) {  // the build's leaf-target records: the keep launch resolves the same targets so
         const int r = ensure_leaf_targets(top, tgt, R.d_tgt.p, top->stream);
         if (r) return r;
@@ -4537,8 +4591,8 @@ int chunk_chains(Topology* top, ReplayReqs& R, int s0, int s1, TraceReqs* rq, F&
     SlotWs ws = R.bws;
     ws.rowflag = R.d_rowflag.p;
     HIPCHK(hipEventRecord(R.ev.e[3], st));
-    HIPCHK(launch_sssp_batch_keep(R.K, R.bcsr, ws, R.d_srcs.p + s0, R.d_srcsh.p + s0, ns, R.kf,
-                                  R.d_tgt.p, (int)top->A, R.delta, R.plan, top->iterGuard,
+    HIPCHK(launch_sssp_batch_keep(R.K, R.bcsr, ws, R.d_srcs.p + s0, R.d_srcsh.p + s0,
+                                  R.d_h0seed.p + s0, ns, R.kf, R.d_tgt.p, (int)top->A, R.delta, R.plan, top->iterGuard,
                                   R.d_bst.p, st));
     HIPCHK(hipEventRecord(R.ev.e[4], st));
     std::vector<uint8_t> fl((size_t)ns), br((size_t)ns, 0);

@@ -323,7 +323,8 @@ hipError_t launch_kprime_resort(uint32_t* adjk, float* kap, float* ksum, float* 
                                 const uint32_t* tbits, const double* K, const KprimeScratch& sc,
                                 hipStream_t stream);
 hipError_t launch_sssp_batch(int K, const DevCSR& g, const SlotWs& ws, const uint32_t* d_sources,
-                             const double* d_srcsh, int nsrc, int kf, const uint32_t* d_targets, int A,
+                             const double* d_srcsh, const double* d_h0seed, int nsrc, int kf,
+                             const uint32_t* d_targets, int A,
                              double delta, const SsspLdsPlan& plan, uint32_t iter_guard,
                              double2* out_lr, uint16_t* out_hops, double* out_rowmin,
                              unsigned long long* d_stats, hipStream_t stream);
@@ -334,7 +335,8 @@ hipError_t launch_sssp_batch(int K, const DevCSR& g, const SlotWs& ws, const uin
 // Afterwards slot b's pair records tagged ep | kPairTagClaim, ep = (counters[4 b] - 1) %
 // kPairTagMask + 1, are the parent chains of batch b: lane j of vertex v at prec[slot][v K + j].
 hipError_t launch_sssp_batch_keep(int K, const DevCSR& g, const SlotWs& ws,
-                                  const uint32_t* d_sources, const double* d_srcsh, int nsrc, int kf,
+                                  const uint32_t* d_sources, const double* d_srcsh,
+                                  const double* d_h0seed, int nsrc, int kf,
                                   const uint32_t* d_targets, int A, double delta,
                                   const SsspLdsPlan& plan, uint32_t iter_guard,
                                   unsigned long long* d_stats, hipStream_t stream);

@@ -107,6 +107,9 @@ struct LdsB {
     double val[kBChunk * K];  // the chunk's source distances, [vertex][source]
     double sh[K];             // per-source bucket shift sh_j = C - pi(s_j)
     double dh0[K];            // per-source d_j(h0) (landmark filter; refreshed per chunk)
+    double hs[K];             // per-source seed of that bound: the prepared d(s_j, h0) scaled up
+                              // past the rounding of either summation order (h0_seed_of,
+                              // topo_core.cpp), so >= the final d_j(h0); +inf = no seed
     double invd;              // 1 / delta
     uint32_t wave[kSsspBlock / 64];
     uint32_t qtail;
@@ -272,6 +275,14 @@ struct BView {
     }
 };
 
+// Source j's upper bound of its final d_j(h0): its tentative value of hub 0 (an upper bound at any
+// time: values only fall) or its seed L.hs[j] (an upper bound from the start), whichever is
+// smaller.  Once the tentative value is final it is <= the seed and takes over.
+template <int K>
+__device__ __forceinline__ double h0_bound(const LdsB<K>& L, const BView<K>& D, uint32_t j) {
+    return fmin(L.hs[j], bits2d(D.get(0u, j)));
+}
+
 struct BBuckets {
     double inv_delta;
     uint32_t cb;       // the bucket being settled
@@ -385,7 +396,7 @@ __device__ __forceinline__ uint32_t load_chunk(const uint32_t* Q, uint32_t cnt, 
             for (int jj = 0; jj < K; jj++) {
                 if (!((m >> jj) & 1u)) continue;
                 L.val[tid * K + jj] = dv[jj];
-                const double h = bits2d(D.get(0u, (uint32_t)jj));
+                const double h = h0_bound(L, D, (uint32_t)jj);
                 const double t = (h - dv[jj]) + 1e-5 * (h + dv[jj] + g.piMax) + 1e-9;
                 T = t > T ? t : T;
             }
@@ -413,7 +424,7 @@ __device__ __forceinline__ uint32_t load_chunk(const uint32_t* Q, uint32_t cnt, 
             if ((L.msk[vi] >> jj) & 1u) L.val[i] = bits2d(D.get(L.vx[vi], jj));
         }
     }
-    if (tid < (uint32_t)K) L.dh0[tid] = bits2d(D.get(0u, tid));
+    if (tid < (uint32_t)K) L.dh0[tid] = h0_bound(L, D, tid);
     __syncthreads();
     if (stats && tid == 0) {
         L.cnt[2] += total;
@@ -485,7 +496,7 @@ __device__ __forceinline__ uint32_t load_sub(uint32_t qv, uint32_t cnt, uint32_t
     const uint32_t lane = threadIdx.x & 63;
     uint32_t deg = 0;
     unsigned long long act = 0;
-    if (lane < K) L.dh0[lane] = bits2d(D.get(0u, lane));  // any value read is a valid bound
+    if (lane < K) L.dh0[lane] = h0_bound(L, D, lane);  // any value read is a valid bound
     if (lane < cnt) {
         const uint32_t v = qv;  // this lane's queue entry (loaded by the caller)
         // every load of the vertex in one round trip: its mask (a queued vertex's is almost
@@ -517,7 +528,7 @@ __device__ __forceinline__ uint32_t load_sub(uint32_t qv, uint32_t cnt, uint32_t
             for (int jj = 0; jj < K; jj++) {
                 if (!((m >> jj) & 1u)) continue;
                 L.val[(wb + lane) * K + jj] = dv[jj];
-                const double h = bits2d(D.get(0u, (uint32_t)jj));
+                const double h = h0_bound(L, D, (uint32_t)jj);
                 const double t = (h - dv[jj]) + 1e-5 * (h + dv[jj] + g.piMax) + 1e-9;
                 T = t > T ? t : T;
             }
@@ -946,7 +957,8 @@ constexpr uint32_t kNoPairS = 0xFFFFFFFFu;
 template <int K, bool DIR, bool KEEP = false>
 __global__ void __launch_bounds__(kSsspBlock, kBatchWgPerCu)
 sssp_batch_kernel(DevCSR g, SlotWs ws, const uint32_t* __restrict__ sources,
-                  const double* __restrict__ srcsh, int nsrc, int kf,
+                  const double* __restrict__ srcsh, const double* __restrict__ h0seed,
+                  int nsrc, int kf,
                   const uint32_t* __restrict__ targets, int A, double delta, uint32_t H,
                   uint32_t P, uint32_t iter_guard,
                   double2* __restrict__ out_lr, uint16_t* __restrict__ out_hops,
@@ -1369,8 +1381,13 @@ sssp_batch_kernel(DevCSR g, SlotWs ws, const uint32_t* __restrict__ sources,
         const uint32_t ep = (iter - 1u) % kTagMask + 1u;
         B.tie_tag = ep | kTagTie;
         if (tid < (uint32_t)K) L.sh[tid] = (int)tid < nk ? srcsh[r0 + tid] : 0.0;
-        // no landmark bound until h0 is reached (the sweeps test kappa0 against L.dh0)
-        if (tid < (uint32_t)K) L.dh0[tid] = INFINITY;
+        // the landmark bound starts at the source's seed (+inf: none until h0 is reached); the
+        // sweeps test kappa0 against L.dh0.  Lanes past the batch's sources hold +inf.
+        if (tid < (uint32_t)K) {
+            const double s0 = (int)tid < nk ? h0seed[r0 + tid] : INFINITY;
+            L.hs[tid] = s0;
+            L.dh0[tid] = s0;
+        }
         if (tid == 0) L.invd = B.inv_delta;
         if (tid == 0) {
             L.fminb = kNoBucket;
@@ -2749,7 +2766,7 @@ SsspLdsPlan sssp_batch_lds_plan(int K, int64_t hub_limit, uint32_t par_hubs, int
 
 template <int K>
 static hipError_t launch_batch_k(const DevCSR& g, const SlotWs& ws, const uint32_t* d_sources,
-                                 const double* d_srcsh, int nsrc, int kf, const uint32_t* d_targets,
+                                 const double* d_srcsh, const double* d_h0seed, int nsrc, int kf, const uint32_t* d_targets,
                                  int A, double delta, const SsspLdsPlan& plan, uint32_t iter_guard,
                                  double2* out_lr, uint16_t* out_hops, double* out_rowmin,
                                  unsigned long long* d_stats, hipStream_t stream) {
@@ -2769,28 +2786,28 @@ static hipError_t launch_batch_k(const DevCSR& g, const SlotWs& ws, const uint32
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kSsspBlock), plan.bytes, stream, g,
-                       ws, d_sources, d_srcsh, nsrc, kf, d_targets, A, delta, plan.H, plan.P, iter_guard,
+                       ws, d_sources, d_srcsh, d_h0seed, nsrc, kf, d_targets, A, delta, plan.H, plan.P, iter_guard,
                        out_lr, out_hops, out_rowmin, d_stats);
     return hipGetLastError();
 }
 
 hipError_t launch_sssp_batch(int K, const DevCSR& g, const SlotWs& ws, const uint32_t* d_sources,
-                             const double* d_srcsh, int nsrc, int kf, const uint32_t* d_targets,
+                             const double* d_srcsh, const double* d_h0seed, int nsrc, int kf, const uint32_t* d_targets,
                              int A, double delta, const SsspLdsPlan& plan, uint32_t iter_guard,
                              double2* out_lr, uint16_t* out_hops, double* out_rowmin,
                              unsigned long long* d_stats, hipStream_t stream) {
     switch (K) {
-        case 2: return launch_batch_k<2>(g, ws, d_sources, d_srcsh, nsrc, kf, d_targets, A, delta, plan, iter_guard, out_lr, out_hops, out_rowmin, d_stats, stream);
-        case 4: return launch_batch_k<4>(g, ws, d_sources, d_srcsh, nsrc, kf, d_targets, A, delta, plan, iter_guard, out_lr, out_hops, out_rowmin, d_stats, stream);
-        case 8: return launch_batch_k<8>(g, ws, d_sources, d_srcsh, nsrc, kf, d_targets, A, delta, plan, iter_guard, out_lr, out_hops, out_rowmin, d_stats, stream);
-        case 16: return launch_batch_k<16>(g, ws, d_sources, d_srcsh, nsrc, kf, d_targets, A, delta, plan, iter_guard, out_lr, out_hops, out_rowmin, d_stats, stream);
+        case 2: return launch_batch_k<2>(g, ws, d_sources, d_srcsh, d_h0seed, nsrc, kf, d_targets, A, delta, plan, iter_guard, out_lr, out_hops, out_rowmin, d_stats, stream);
+        case 4: return launch_batch_k<4>(g, ws, d_sources, d_srcsh, d_h0seed, nsrc, kf, d_targets, A, delta, plan, iter_guard, out_lr, out_hops, out_rowmin, d_stats, stream);
+        case 8: return launch_batch_k<8>(g, ws, d_sources, d_srcsh, d_h0seed, nsrc, kf, d_targets, A, delta, plan, iter_guard, out_lr, out_hops, out_rowmin, d_stats, stream);
+        case 16: return launch_batch_k<16>(g, ws, d_sources, d_srcsh, d_h0seed, nsrc, kf, d_targets, A, delta, plan, iter_guard, out_lr, out_hops, out_rowmin, d_stats, stream);
     }
     return hipErrorInvalidValue;
 }
 
 template <int K>
 static hipError_t launch_keep_k(const DevCSR& g, const SlotWs& ws, const uint32_t* d_sources,
-                                const double* d_srcsh, int nsrc, int kf, const uint32_t* d_targets,
+                                const double* d_srcsh, const double* d_h0seed, int nsrc, int kf, const uint32_t* d_targets,
                                 int A, double delta, const SsspLdsPlan& plan, uint32_t iter_guard,
                                 unsigned long long* d_stats, hipStream_t stream) {
     if (kf < 1 || kf > K || nsrc < 0 || A < 0) return hipErrorInvalidValue;
@@ -2806,21 +2823,21 @@ static hipError_t launch_keep_k(const DevCSR& g, const SlotWs& ws, const uint32_
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBMaxLds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(nb), dim3(kSsspBlock), plan.bytes, stream, g, ws, d_sources,
-                       d_srcsh, nsrc, kf, d_targets, A, delta, plan.H, plan.P, iter_guard,
+                       d_srcsh, d_h0seed, nsrc, kf, d_targets, A, delta, plan.H, plan.P, iter_guard,
                        (double2*)nullptr, (uint16_t*)nullptr, (double*)nullptr, d_stats);
     return hipGetLastError();
 }
 
 hipError_t launch_sssp_batch_keep(int K, const DevCSR& g, const SlotWs& ws,
-                                  const uint32_t* d_sources, const double* d_srcsh, int nsrc, int kf,
+                                  const uint32_t* d_sources, const double* d_srcsh, const double* d_h0seed, int nsrc, int kf,
                                   const uint32_t* d_targets, int A, double delta,
                                   const SsspLdsPlan& plan, uint32_t iter_guard,
                                   unsigned long long* d_stats, hipStream_t stream) {
     switch (K) {
-        case 2: return launch_keep_k<2>(g, ws, d_sources, d_srcsh, nsrc, kf, d_targets, A, delta, plan, iter_guard, d_stats, stream);
-        case 4: return launch_keep_k<4>(g, ws, d_sources, d_srcsh, nsrc, kf, d_targets, A, delta, plan, iter_guard, d_stats, stream);
-        case 8: return launch_keep_k<8>(g, ws, d_sources, d_srcsh, nsrc, kf, d_targets, A, delta, plan, iter_guard, d_stats, stream);
-        case 16: return launch_keep_k<16>(g, ws, d_sources, d_srcsh, nsrc, kf, d_targets, A, delta, plan, iter_guard, d_stats, stream);
+        case 2: return launch_keep_k<2>(g, ws, d_sources, d_srcsh, d_h0seed, nsrc, kf, d_targets, A, delta, plan, iter_guard, d_stats, stream);
+        case 4: return launch_keep_k<4>(g, ws, d_sources, d_srcsh, d_h0seed, nsrc, kf, d_targets, A, delta, plan, iter_guard, d_stats, stream);
+        case 8: return launch_keep_k<8>(g, ws, d_sources, d_srcsh, d_h0seed, nsrc, kf, d_targets, A, delta, plan, iter_guard, d_stats, stream);
+        case 16: return launch_keep_k<16>(g, ws, d_sources, d_srcsh, d_h0seed, nsrc, kf, d_targets, A, delta, plan, iter_guard, d_stats, stream);
     }
     return hipErrorInvalidValue;
 }
