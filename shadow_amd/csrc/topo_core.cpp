@@ -12,27 +12,17 @@
 //   * attach uses a candidate index built once instead of an O(V) scan per host.
 #include <arpa/inet.h>
 #include <dlfcn.h>
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
 
-#include <algorithm>
-#include <chrono>
-#include <cmath>
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <memory>
-#include <functional>
 #include <numeric>
 #include <queue>
-#include <thread>
 #include <unordered_set>
-#include <vector>
 
-#include "../../include/shd_topology_abi.h"
-#include "topo_internal.h"
+#include "topo_host.h"
 
 // ---- imports from the Shadow executable (weak: absent in a standalone process) ----
 extern "C" {
@@ -78,13 +68,10 @@ void pinned_free(void* p) {
     }
     free(p);
 }
-}  // namespace shdtopo
-
-namespace {
 
 // Standalone filter (no Shadow logger): SHDTOPO_LOG = 0 silent, 1 critical + warning (default),
 // 2 + message, 3 + info
-int log_level() {
+static int log_level() {
     static int lvl = [] {
         const char* e = getenv("SHDTOPO_LOG");
         return e ? atoi(e) : 1;
@@ -92,13 +79,6 @@ int log_level() {
     return lvl;
 }
 
-// GLib log levels (G_LOG_LEVEL_CRITICAL / WARNING / MESSAGE / INFO)
-[[maybe_unused]] constexpr int kLogCritical = 1 << 3, kLogWarning = 1 << 4, kLogMessage = 1 << 5,
-                                kLogInfo = 1 << 6;
-
-// The reference's critical() / warning() / message() (shd-logging.h:24-59): inside Shadow the
-// message goes through logging_log, which filters by the configured level and adds the run's
-// prefix; standalone it goes to stderr, filtered by SHDTOPO_LOG.
 void shd_log(int glevel, const char* file, const char* func, int line, const char* fmt, ...) {
     const int lvl = glevel <= kLogWarning ? 1 : (glevel == kLogMessage ? 2 : 3);
     if (!logging_log && lvl > log_level()) return;
@@ -116,458 +96,13 @@ void shd_log(int glevel, const char* file, const char* func, int line, const cha
                       : glevel == kLogMessage ? "message" : "info";
     fprintf(stderr, "[shdtopo] %s: %s\n", tag, buf);
 }
-#define CRITICAL(...) shd_log(kLogCritical, __FILE__, __FUNCTION__, __LINE__, __VA_ARGS__)
-#define WARNING(...) shd_log(kLogWarning, __FILE__, __FUNCTION__, __LINE__, __VA_ARGS__)
-#define MESSAGE(...) shd_log(kLogMessage, __FILE__, __FUNCTION__, __LINE__, __VA_ARGS__)
-#define INFO(...) shd_log(kLogInfo, __FILE__, __FUNCTION__, __LINE__, __VA_ARGS__)
-
-#define HIPCHK(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess) {                                                             \
-            CRITICAL("HIP error %s at %s:%d (%s)", hipGetErrorString(_e), __FILE__, __LINE__, \
-                     #expr);                                                                \
-            return -100 - (int)_e;                                                          \
-        }                                                                                   \
-    } while (0)
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    ~DevBuf() { release(); }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    hipError_t ensure(size_t count) {
-        if (count <= n && p) return hipSuccess;
-        release();
-        hipError_t e = hipMalloc(&p, sizeof(T) * (count ? count : 1));
-        if (e == hipSuccess) n = count;
-        else p = nullptr;
-        return e;
-    }
-};
-
-// Open-addressing IP -> vertex table read by the getters without a lock (Shadow calls them from
-// every worker thread, shd-worker.c:179-203; the reference takes virtualIPLock per lookup,
-// shd-topology.c:514-531).  A slot holds (ip << 32) | (vertex + 2); 0 = empty, low word kTomb =
-// detached.  An IP keeps its slot for the table's lifetime, so a lookup stops at its key or at an
-// empty slot.  Writers (attach / detach) are serialised by Topology::ipMu.
-struct IpTable {
-    static constexpr uint32_t kTomb = 0xFFFFFFFFu;
-    uint64_t mask = 0;
-    size_t used = 0;
-    std::unique_ptr<std::atomic<uint64_t>[]> slot;
-    explicit IpTable(uint64_t cap) : mask(cap - 1), slot(new std::atomic<uint64_t>[cap]) {
-        for (uint64_t i = 0; i < cap; i++) slot[i].store(0, std::memory_order_relaxed);
-    }
-    uint64_t home(uint32_t ip) const { return ((uint64_t)ip * 0x9E3779B97F4A7C15ull >> 17) & mask; }
-    int32_t find(uint32_t ip) const {
-        for (uint64_t i = home(ip);; i = (i + 1) & mask) {
-            const uint64_t w = slot[i].load(std::memory_order_acquire);
-            if (w == 0) return -1;
-            if ((uint32_t)(w >> 32) == ip) {
-                const uint32_t lo = (uint32_t)w;
-                return lo == kTomb ? -1 : (int32_t)(lo - 2);
-            }
-        }
-    }
-    // writer: the slot of ip (existing, else the first empty one)
-    uint64_t place(uint32_t ip) const {
-        for (uint64_t i = home(ip);; i = (i + 1) & mask) {
-            const uint64_t w = slot[i].load(std::memory_order_relaxed);
-            if (w == 0 || (uint32_t)(w >> 32) == ip) return i;
-        }
-    }
-};
 
 uint64_t next_topology_uid() {
     static std::atomic<uint64_t> n{0};
     return n.fetch_add(1) + 1;
 }
 
-// link monitors (shdtopo_monitor_*, below): ids are unique in the process, so another topology's
-// id is never found in this one's list
-struct LinkMonitor;
-void monitors_release(Topology* top);
-
-}  // namespace
-
-struct _Topology {
-    // the parsed graph; the peer engines of a multi-GPU build share the owner's (read-only)
-    std::shared_ptr<HostGraph> gp = std::make_shared<HostGraph>();
-    HostGraph& g = *gp;
-    _Topology() = default;
-    explicit _Topology(std::shared_ptr<HostGraph> shared) : gp(std::move(shared)), g(*gp) {}
-
-    bool isComplete = false;
-    bool isDirected = false;
-    bool isPeer = false;  // a peer engine of a multi-GPU build (make_peer), not a caller's topology
-    bool hasMultiEdges = false;
-    // link failure what-if (shdtopo_derive_without): per edge its id in the root topology (empty:
-    // the identity, a root topology), the vertices failed on the way here (empty: none; they are
-    // isolated, exempt from the connectivity check and no attachment candidates), and whether
-    // the derivation already checked the connectivity of the rest
-    std::vector<int32_t> edgeOrigin;
-    std::vector<uint8_t> failedVertex;
-    bool preChecked = false;
-    ShdDiffStats diffStats{};  // table diff (shdtopo_table_diff, topo_diff.hip): first argument's
-
-    // options ("abort_on_error" and "lazy" are read by getters on worker threads without a lock)
-    std::atomic<bool> abortOnError{true};
-    std::atomic<bool> lazy{true};
-    double delta = 0.0;  // 0 = auto
-    int slotsOpt = 0;
-    int device = 0;
-    int64_t hubLimit = -1;  // LDS-cached hub distances (-1 = fill the LDS)
-    int64_t parHubs = 2048; // hubs whose parent is hinted during the SSSP (0 = always scan)
-    uint32_t rsChunk = kRowScanCap;  // pairs per parent-pass row-scan chunk
-    int batchK = 8;         // sources per SSSP workgroup (sssp_batch_kernel<K>, K in {2,4,8,16})
-    uint32_t iterGuard = 4000000u;  // near iterations per batch before the kernel gives up
-                                    // (option "iter_guard": a test hook for the -4 error path)
-
-    // attach state (shd-topology.c:20-24 virtualIP)
-    std::shared_mutex ipMu;
-    std::unordered_map<uint32_t, int32_t> virtualIP;
-    AttachIndex aidx;
-    // the getters' lock-free view of virtualIP (IpTable): written under ipMu (exclusive) next to
-    // the map, read with acquire loads and no lock; superseded tables stay allocated until free
-    std::atomic<IpTable*> ipTab{nullptr};
-    std::vector<std::unique_ptr<IpTable>> ipTabs;
-    const uint64_t uid = next_topology_uid();  // identifies this topology to thread-local caches
-
-    // table geometry
-    std::mutex buildMu;
-    // writers of the device table (builds, binds) hold it exclusively inside buildMu; the getters'
-    // row copies (snap_row) hold it shared, so they run in parallel and never see a half-built table
-    std::shared_mutex tabMu;
-    std::atomic<bool> tableValid{false};
-    std::vector<int32_t> attached;  // columns: distinct attached vertices, ascending
-    std::vector<int32_t> colOf;     // vertex -> column
-    std::shared_ptr<const std::vector<int32_t>> colOfShared;  // colOf for the snapshots (lazily
-                                                              // made, reset with the geometry)
-    int64_t A = 0;
-
-    // device state
-    bool devInit = false;
-    // any entry point asked this engine's device for work (every one goes through dev_init): the
-    // "device" option is fixed from then on (buffers, tables and matrices live on that device)
-    bool deviceUsed = false;
-    int devId = 0;               // the device dev_init bound (every later entry re-binds it)
-    int64_t devInits = 0;        // dev_init runs (a "device" change before the first attach
-                                 // re-initialises on the new device)
-    // Device init at topology_new (shd-topology.c:1237): a background thread holding buildMu
-    // initialises the default device (SHDTOPO_DEVICE, else 0) while the GraphML is parsed, so the
-    // first attach and the first build no longer pay the HIP context, queues and code objects.
-    std::thread initThread;
-    double initBgMs = 0.0;       // its wall time
-    // Preparation at the first attach (option "prepare_on_attach", default on): a background
-    // thread initialises the device and prepares the graph (upload_csr) under buildMu while the
-    // host attaches its hosts, so the first table build -- whose lock waits for the thread --
-    // no longer pays them.  The device option must be set before the first attach.
-    bool prepOnAttach = true;
-    // Preparation at topology_new: a non-complete topology loaded from
-    // GraphML starts the same thread right after the parse, so the attach phase and everything
-    // Shadow does before it hide it (C4: ~50 ms); a later "device" change re-prepares there.
-    // SHDTOPO_NO_LOAD_PREP=1 leaves it to the first attach.
-    bool prepOnLoad = false;  // the running / finished preparation was started by topology_new
-    std::atomic<bool> prepStarted{false};
-    std::thread prepThread;
-    double prepBgMs = 0.0;       // the thread's wall time
-    double prepStepMs[4] = {0, 0, 0, 0};  // of which device init, graph preparation, edge scan,
-                                          // SSSP workspace
-    // wall clock of the first attach, and whether the first table since then was installed
-    // (ShdStats.first_attach_to_table_ms)
-    std::chrono::steady_clock::time_point firstAttachT;
-    std::atomic<bool> firstAttachSet{false};
-    bool firstTableDone = false;
-    int prepBgRc = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
-    bool csrUploaded = false;
-    bool rowsSorted = false;
-    // host side of the graph preparation (upload_csr): shared with the peer engines of a
-    // multi-GPU build, which copy the device CSR from this engine instead of preparing it again
-    std::shared_ptr<HostPrep> hp;
-    int64_t csrHostRuns = 0;    // host-side preparations (peers that copied count none)
-    // per vertex, 32 B: {parent, slot of (v -> parent) in v's row, f64 latency, f64 loss, pad}
-    DevBuf<uint32_t> d_spt;
-    DevBuf<uint32_t> d_sptPar;  // per vertex: h0-tree parent
-    // the parsed edge arrays (document order) and old -> new ids, kept in HBM after the graph
-    // preparation: the heap replay's CSR is built from them (prep_replay_csr)
-    DevBuf<int32_t> d_eu, d_ev;
-    DevBuf<double> d_elat, d_eloss;
-    DevBuf<uint32_t> d_inv;
-    int wsK = 0;                // batch width the workspace was laid out for
-    uint32_t wsHubRows = 0;     // rows [0, wsHubRows) of every slot's dist block may hold a
-                                // launch's hub distances (the epilogue copies them there): a
-                                // launch with fewer LDS hubs refills [H, wsHubRows) with +inf
-    int64_t wsRing = 0;
-    size_t wsHpar = 0;          // hub-hint entries per slot the workspace was sized for
-    uint32_t wsRsChunk = 0;     // row-scan chunk the workspace was sized for
-    DevBuf<uint32_t> d_rowptr, d_adj;
-    // directed topologies: d_rowptr / d_adjo are the out-rows (relaxation, kappa copy, target
-    // fixpoint), d_rowptrIn / d_adj / d_aloss the in-rows (parent pass); undirected ones use
-    // d_rowptr / d_adj for both (d_adjo, d_rowptrIn empty) -- adj_out(), rowptr_in()
-    DevBuf<uint32_t> d_adjo, d_rowptrIn;
-    DevBuf<uint32_t> d_adjk;  // rows re-sorted by kappa = w - pi(col) (batch relaxation copy)
-    DevBuf<float> d_kap, d_ksum, d_kap0;  // kappa of d_adjk (f32, rounded down), per-vertex probes
-    double meanLat = -1.0;
-    double minLat = 0.0;  // smallest non-loop edge latency (edge_scan): the landmark's bucket gap
-    uint64_t ipGen = 1, geomGen = 0;  // attach/detach generation; compute_geometry's copy  // mean non-loop edge latency (default delta), computed once
-    DevBuf<double> d_aloss, d_vloss, d_selfLat, d_selfLoss;
-    DevBuf<unsigned long long> d_dist, d_qa, d_qb;
-    DevBuf<uint32_t> d_ring;
-    DevBuf<uint4> d_prec;  // per (vertex, source) pair records of the parent pass
-    DevBuf<double> d_pathbuf;
-    DevBuf<uint32_t> d_counters;
-    DevBuf<uint4> d_rscan;  // parent pass row-scan records, rsChunk x K per slot
-    int slots = 0;
-    DevBuf<double2> d_lr;
-    DevBuf<uint16_t> d_hops;
-    // a table installed in place (shdtopo_bind_table_ref): caller-owned HBM read instead of d_lr /
-    // d_hops until the next build or bind
-    const double2* extLr = nullptr;
-    const uint16_t* extHops = nullptr;
-    DevBuf<double> d_rowmin;
-    DevBuf<double> d_elatAA, d_elossAA, d_vlossA;
-    std::vector<int32_t> aaCols;  // the columns the resident A x A edge matrices were built for
-    DevBuf<uint32_t> d_sources, d_targets;
-    DevBuf<double> d_srcsh;
-    DevBuf<double> d_h0seed;  // per layout position: the landmark bound's seed (source_h0_seeds)
-    DevBuf<uint8_t> d_mask;
-    DevBuf<uint32_t> d_hpar;
-    DevBuf<unsigned long long> d_stats;
-    // host-batch staging
-    DevBuf<int32_t> b_src, b_dst;
-    DevBuf<uint32_t> b_pay, b_sin, b_sout;
-    DevBuf<uint64_t> b_now, b_time;
-    DevBuf<uint8_t> b_dl;
-
-    // exact heap replay (topo_replay.hip): igraph's pop order for rows whose target chains cross
-    // a d-tied parent, and every row of a directed topology
-    bool tieReplay = true;    // option "tie_replay" (0: report ambiguous pairs only)
-    bool replayAll = false;   // option "replay_all" (test hook: every row through the replay)
-    // option "tie_dense": -1 auto, 0 never, 1 always.  A tie-dense topology (integer latencies:
-    // C4-int replays every row) skips the batch kernel, whose rows the replay would recompute
-    // anyway; auto turns it on after a build of >= 64 rows that replayed >= 90 % of them, or
-    // before the first batched build of an integer-latency topology when a probe of
-    // kTieProbeRows sample rows (batch kernel) finds >= 90 % of them crossing a tie.
-    int tieDenseOpt = -1;
-    bool tieDense = false;
-    bool tieProbed = false;
-    DevBuf<uint32_t> d_probeSrc;
-    DevBuf<double> d_probeSh;
-    DevBuf<double> d_probeSeed;
-    int replaySlotsOpt = 0;   // option "replay_slots" (0 = sized from the CUs and free HBM)
-    int replayWpc = 20;       // option "replay_wpc": replay wavefronts per CU (LDS and HBM allowing)
-    bool rwsInt = false;      // the replay workspace's node block is laid out for u32 keys
-    bool replayLandmark = true;  // option "replay_landmark": skip edges into vertices the
-                                 // landmark bound proves popped (topo_replay.hip)
-    bool replayIntOpt = true;    // option "replay_int_keys": u32 heap keys when replayIntOk
-    bool replayIntOk = false;    // every latency an integer and V x max < 2^32 - 1 (upload_replay)
-    int sourceOrder = 2;      // option "source_order": batch kernel source grouping (0 = row
-                              // order, 1 = by the hub their h0-tree path enters the core, then
-                              // pi, 2 = preorder of the h0 shortest-path tree)
-    int batchFill = 0;        // option "batch_fill": sources per batch (0 = auto: the fewest per
-                              // batch that finish the rows in the same rounds of the slots)
-    int batchOrder = 5;       // option "batch_order": 0 grouped order, 1 shuffled, 2 / 3 by mean
-                              // pi descending / ascending, 4 by mean h0-tree depth descending,
-                              // 5 auto (4 past 3 rounds of the slots, else 2)
-    bool targetSkip = true;   // option "target_skip": target bits in the relaxation copy; pairs
-                              // into non-target tail vertices that would expand nothing are
-                              // dropped (topo_sssp_batch.hip)
-    std::vector<uint32_t> adjkTargets;  // the target set whose bits d_adjk carries
-    bool leafTargets = true;   // option "leaf_targets": a target with one non-loop edge is resolved
-                               // from its uplink (undirected topologies; topo_sssp_batch.hip)
-    bool adjkLeaf = false;     // d_adjk's target-derived content is that of the effective target
-                               // set: (adjkTargets - peeled) + uplinks, peeled vertices dead
-    bool h0Seed = true;        // option "h0_seed": the batch kernel's landmark bound d_j(h0) starts
-                               // at the prepared d(s_j, h0) (h0_seed_of) instead of +inf
-    std::vector<uint32_t> leafFor;  // the target set d_tleaf / d_tbitsEff / d_dead belong to
-    int64_t leafPeeled = 0;         // ... and its peeled targets
-    bool adjkFlagged = false;
-    bool adjkPlain = false;    // d_adjk / d_kap / d_ksum / d_kap0 are the plain kappa-sorted copy
-    bool adjkResorted = false; // ... re-sorted by the target-aware key of adjkTargets
-    bool targetResort = true;  // option "target_resort": rows of the relaxation copy re-sorted
-                               // by the target-aware key per target set (kappa-prefix cuts stop
-                               // before heads that relax nothing reaching a target)
-    int targetKappa = 6;      // option "target_kappa": iterations of the target-aware kappa
-                              // fixpoint written into the relaxation copy (0: kappa0).  C4 kernel:
-                              // 2 iterations 226 ms, 4: 199, 6: 194, 12: 194, 32: 196 (no
-                              // fixpoint is reached: cycles without targets rise forever; every
-                              // iterate is exact)
-    DevBuf<double> d_pot, d_kfA, d_kfB, d_kfPart;
-    DevBuf<double> d_kfKap;   // the out-rows' static w - pi(y) of the kappa fixpoint
-    const double* kfFinal = nullptr;  // d_kfA or d_kfB: the last iterate [K | Kt] of the target
-                                      // preparation d_adjk carries (shdtopo_export_prep)
-    bool kfKapReady = false;
-    // the target-aware re-sort's scratch (KprimeScratch), kept: the first build's target
-    // preparation allocates nothing (the background preparation sizes it)
-    DevBuf<float> d_kpKey;
-    DevBuf<uint32_t> d_kpIdx;
-    DevBuf<uint4> d_kpRec;
-    DevBuf<uint8_t> d_kpTmp;
-    // the rows longer than kSegBlock (SegBig): their entries' positions and row ordinals, the
-    // radix sort's key / value buffers
-    DevBuf<uint32_t> d_kpBigPos, d_kpBigRow, d_kpBigVal;
-    DevBuf<unsigned long long> d_kpBigKey;
-    int64_t kpBig = -1;  // their entries (-1: not listed yet)
-    int kpBigBits = 33;
-    // the target preparation runs asynchronously (overlapping the host's source order): its
-    // iteration count and event time are read after the build's next stream sync
-    bool tpPending = false;
-    hipEvent_t evp0 = nullptr, evp1 = nullptr;
-    // hub rows cut into segments (HubSegs): {row, first entry} and the rows cut in several
-    DevBuf<uint2> d_hseg;
-    DevBuf<uint4> d_hmulti;
-    uint32_t hsegRows = 0, hsegN = 0, hmultiN = 0;
-    int slotsUsed = 0;  // workgroups of the last batched launch (<= slots)
-    DevBuf<unsigned int> d_kfChanged;
-    DevBuf<uint32_t> d_rowmap, d_bsrc;  // batch order: output row and source of each position
-    // cache of the last batch order (enqueue_rows): the rows' sources, batch fill and options
-    std::vector<uint32_t> ordSrc;
-    std::vector<uint32_t> ordBase;  // positions in the grouping order (source_order)
-    std::vector<uint32_t> ordPerm;  // ... then batches in batch_order
-    bool ordUploaded = false;       // d_rowmap / d_bsrc / d_srcsh hold ordPerm's layout
-    const HostPrep* ordHp = nullptr;
-    // measured batch layout (option "balance"): per vertex the cost of a
-    // source in its batch (wall-clock ticks, EMA over the builds; 0 = none yet), and a batch's
-    // fixed cost; the positions' sources and batch starts of the uploaded layout
-    int balance = 1;  // 2: costs frozen after the first build (diagnostic)
-    int64_t lastBatches = 0;
-    std::vector<float> srcCost;
-    const HostPrep* costHp = nullptr;
-    double costA = 0.0;
-    std::vector<uint32_t> layPsrc;
-    DevBuf<uint32_t> d_bstart;
-    DevBuf<unsigned long long> d_btrace;
-    int ordKf = -1, ordSO = -1, ordBO = -1;
-    double ordDelta = -1.0;
-    double ordPhase = -2.0;
-    // option "h0_phase": where the landmark h0 sits in its bucket (the fraction of the bucket
-    // below its shifted distance, which is the same for every source).  Unset: h0 closes its
-    // bucket with a gap of min(0.01 delta, minLat / 2) to the bucket's end, so no neighbour of h0
-    // shares its bucket and the hub core around it is expanded in the next bucket with d(h0)
-    // final and the landmark bound tight.  < 0: the round-4 shifts (sh =
-    // piMax - pi(s) + 2 delta, h0's phase whatever piMax / delta gives)
-    double h0Phase = 0.99;
-    bool h0PhaseSet = false;
-    bool replayUploaded = false;
-    int64_t rnadj = 0;  // entries of the replay CSR
-    DevBuf<uint32_t> d_rrow;
-    DevBuf<uint4> d_rrec;
-    DevBuf<uint32_t> d_rown;
-    DevBuf<double2> d_rhop;
-    DevBuf<uint32_t> d_tbits;
-    // leaf targets (ensure_leaf_targets): the records, the effective target bitmap, the peeled
-    // vertices' bitmap, their count
-    DevBuf<uint4> d_tleaf;
-    DevBuf<uint32_t> d_tbitsEff, d_dead, d_leafCount;
-    DevBuf<uint4> d_rvrec, d_rnode;
-    DevBuf<uint32_t> d_rpath, d_rrows;
-    DevBuf<uint8_t> d_rowflag;
-    int rslots = 0;
-    int rslotsUse = 0;      // replay wavefronts of the next launch (<= rslots)
-    hipEvent_t evr0 = nullptr, evr1 = nullptr;
-    bool replayPending = false;
-
-    // route tracing (shdtopo_trace_routes, topo_trace.hip): ids the replay CSR does not carry,
-    // uploaded by the first trace -- relabelled -> original vertex, the igraph_get_eid edge of
-    // every replay-CSR entry, the lowest-id self loop of every vertex
-    int traceChunk = 0;       // option "trace_chunk": sources per replay launch (0 = the slots)
-    int traceBatch = 1;       // option "trace_batch": 1 = chains from the batch kernel's pair
-                              // records where eligible (prepare_batch_path), 0 = always replay
-    bool traceIdsReady = false;
-    DevBuf<int32_t> d_tperm, d_reid, d_selfEid;
-    ShdTraceStats traceStats{};  // the last trace's own counters
-    // link load (shdtopo_link_load, topo_load.hip)
-    int loadWalk = 1;            // option "load_walk": 1 = the per-request walk (the default:
-                                 // DESIGN.md 3.7), 0 = the leaf-to-root tree accumulation
-    ShdLoadStats loadStats{};    // the last call's own counters
-    ShdCrossStats crossStats{};  // link crossings (shdtopo_link_crossings, topo_cross.hip)
-    ShdTimelineStats timelineStats{};  // link timeline (shdtopo_link_timeline, topo_timeline.hip)
-    // link monitors (shdtopo_monitor_*, topo_monitor.hip): {id, monitor}; option
-    // "monitor_index_mb" (0 = half of the free device memory at prepare)
-    std::vector<std::pair<int, LinkMonitor*>> monitors;
-    double monitorIndexMb = 0.0;
-
-    // multi-GPU build inside the library (one Shadow process): device d builds
-    // rows [d*R, (d+1)*R) with its own stream / workspace (a peer Topology on that device),
-    // RCCL all-gathers the rows into every device's table and all-reduces the minimum
-    int devicesOpt = 1;        // option "devices"
-    int xchgMode = 0;          // option "exchange": 0 auto (RCCL across distinct devices, else
-                               // push), 1 RCCL all-gather, 2 push (peer DMA as each shard ends)
-    hipStream_t xstream = nullptr;  // exchange stream of a push exchange
-    // the getters' row copies (snap_row): a few streams shared by the worker threads, made by
-    // dev_init (the background init) so that no query pays a stream creation
-    static constexpr int kCopyStreams = 16;
-    hipStream_t cstream[kCopyStreams] = {};
-    int memShareDiv = 1;       // engines of this build sharing this engine's physical device: its
-                               // workspaces take that share of the device's free memory
-    bool forceRccl = false;    // option "rccl": the RCCL exchange even with one device (tests)
-    std::vector<Topology*> peers;      // devices 1..N-1
-    std::vector<ncclComm_t> comms;     // one per device, ncclCommInitAll
-    std::vector<int> commDevs;
-    int64_t shardRows = 0;
-
-    // host mirror of the table for the per-call getters: an immutable snapshot swapped atomically
-    // (getters on worker threads never see a table being rebuilt)
-    std::shared_ptr<const HostTable> snap;
-    std::atomic<int64_t> rowsToHost{0};      // ShdStats.rows_to_host
-    std::atomic<int64_t> rowsToHostNs{0};    // ShdStats.rows_to_host_ms
-    double eagerMin = -1.0;
-
-    // attached-set generations: setGen bumps whenever a vertex gains its first or loses its last
-    // host (the table's columns change); tableGen = the setGen the device table was built for
-    std::atomic<uint64_t> setGen{1};
-    std::atomic<uint64_t> tableGen{0};  // written under buildMu, read lock-free by table_current
-    std::atomic<uint64_t> tableSerial{0};  // bumps on every device table build / bind
-    bool geomInit = false;
-
-    // lazy emulation.  SSSP branch: the reference's cache holds (s, t) iff
-    // row s was computed (computeSourcePaths) at a moment t was attached; rows are recomputed on
-    // a miss.  Epochs are ipGen values: per vertex the attach intervals [start, end) of "at
-    // least one host on it", per source vertex the epochs it was materialised at.
-    std::vector<uint32_t> hostsOn;                             // hosts per vertex (ipMu)
-    // window adapters registered (shdtopo_window_hold) and the vertices that lost their last
-    // host since the last flush: they stay table columns until shdtopo_window_release (ipMu)
-    int windows = 0;
-    std::vector<int32_t> deferredOff;
-    std::unordered_map<int32_t, std::vector<std::pair<uint64_t, uint64_t>>> ivals;  // (ipMu)
-    std::atomic<uint64_t> lastNewEpoch{0};                     // latest interval start
-    std::unique_ptr<std::atomic<uint64_t>[]> matGen;          // per vertex: latest epoch
-    std::unordered_map<int32_t, std::vector<uint64_t>> matEpochs;  // all epochs (lazyMu)
-    std::unordered_map<int32_t, double> matMin;  // the row minimum its latest one offered (lazyMu)
-    std::mutex lazyMu;
-    // per (column pair) bit of the complete branch, for one geometry; superseded arrays stay
-    // allocated (getters read the current one without a lock)
-    struct PairBits {
-        size_t words = 0;
-        std::unique_ptr<std::atomic<uint64_t>[]> bits;
-    };
-    std::atomic<PairBits*> matPair{nullptr};
-    std::vector<std::unique_ptr<PairBits>> matPairs;
-    std::mutex minMu;
-    double lazyMin = 0.0;  // top->minimumPathLatency
-
-    // the reference's shortestPathTotalTime / shortestPathCount (shd-topology.c:46-47,792-793),
-    // logged when the topology is freed (:445-446): rows built and the builds' wall time
-    double spTotalSec = 0.0;
-    uint64_t spCount = 0;
-
-    // stats
-    bool rowsPending = false;  // a launch whose stats have not been read back yet
-    bool routePending = false;
-    ShdStats stats{};
-    std::chrono::steady_clock::time_point bstepT;
-};
-
-namespace {
-
+// (external linkage: topo_host.h declares what topo_flows.cpp and topo_monitor_host.cpp call)
 void edge_scan(Topology* top);
 
 void fatal_or_continue(Topology* top, const char* what) {
@@ -680,7 +215,6 @@ bool check_graph(Topology* top) {
     return true;
 }
 
-extern "C" void topology_free(Topology* top);
 void start_device_init(Topology* top);
 
 Topology* finish_new(Topology* top) {
@@ -3260,9 +2794,6 @@ void host_off(Topology* top, int32_t v) {
     }
 }
 
-// shd-topology.c:1154-1166: g_hash_table_replace(virtualIP, ip, vertex)
-int ensure_workspace(Topology* top, int nsrc);
-
 // The attach-time preparation (Topology::prepOnAttach): device init + graph preparation in a
 // background thread holding buildMu; a build (or any other buildMu holder) that comes first does
 // the work itself and the thread then finds nothing left to do.  Complete topologies have no
@@ -3340,6 +2871,7 @@ void release_prepared(Topology* top) {
     top->hp.reset();
 }
 
+// shd-topology.c:1154-1166: g_hash_table_replace(virtualIP, ip, vertex)
 void do_attach(Topology* top, uint32_t ip, int32_t v, uint64_t* bwDownOut, uint64_t* bwUpOut) {
     if (!top->firstAttachSet.load(std::memory_order_relaxed)) {
         std::unique_lock<std::shared_mutex> lk(top->ipMu);
@@ -3379,7 +2911,7 @@ void do_detach(Topology* top, uint32_t ip) {
     if (v >= 0) host_off(top, v);
 }
 
-}  // namespace
+}  // namespace shdtopo
 
 // =============================================================================================
 // C ABI
@@ -4196,2060 +3728,6 @@ int shdtopo_replay_source(Topology* top, int32_t srcv, int full, double* dist, i
     return 0;
 }
 
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------
-// route tracing (include/shd_topology_abi.h shdtopo_trace_routes; kernels in topo_trace.hip)
-// ---------------------------------------------------------------------------------------------
-namespace {
-
-static_assert(sizeof(ShdRoute) == 32 && sizeof(TraceRoute) == sizeof(ShdRoute) &&
-                  offsetof(ShdRoute, hops) == offsetof(TraceRoute, hops) &&
-                  offsetof(ShdRoute, status) == offsetof(TraceRoute, status) &&
-                  offsetof(ShdRoute, latency) == offsetof(TraceRoute, latency) &&
-                  offsetof(ShdRoute, reliability) == offsetof(TraceRoute, reliability),
-              "TraceRoute is the device image of ShdRoute");
-
-ShdRoute route_blank(int status) {
-    ShdRoute r;
-    r.offset = -1;
-    r.hops = -1;
-    r.status = status;
-    r.latency = -1.0;
-    r.reliability = -1.0;
-    return r;
-}
-
-// The call's offsets on the host (complete topologies): the running sum of hops + 1 over the
-// traced requests in request order; a route that does not fit below cap entirely gets status 3.
-int64_t place_routes_host(ShdRoute* routes, int64_t n, int64_t cap) {
-    int64_t off = 0;
-    for (int64_t i = 0; i < n; i++) {
-        if (routes[i].status != kTraceOk) continue;
-        const int64_t need = (int64_t)routes[i].hops + 1;
-        if (off + need <= cap) {
-            routes[i].offset = off;
-        } else {
-            routes[i].offset = -1;
-            routes[i].status = kTraceCap;
-        }
-        off += need;
-    }
-    return off;
-}
-
-// _topology_lookupPath (shd-topology.c:835-873) with its route: one hop over the igraph_get_eid
-// edge (lowest id) of the pair, the self loop for a self pair.  Host only: the parsed graph.
-// the igraph_get_eid edge (lowest id; -1 = none) of every (sv[i], dv[i]) with both ends attached
-std::vector<int32_t> complete_pair_eids(Topology* top, const std::vector<int32_t>& sv,
-                                        const std::vector<int32_t>& dv, int64_t n) {
-    const HostGraph& g = top->g;
-    auto key = [](int32_t a, int32_t b) { return ((uint64_t)(uint32_t)a << 32) | (uint32_t)b; };
-    std::unordered_map<uint64_t, int32_t> eidOf;
-    for (int64_t i = 0; i < n; i++)
-        if (sv[(size_t)i] >= 0 && dv[(size_t)i] >= 0) eidOf.emplace(key(sv[(size_t)i], dv[(size_t)i]), -1);
-    for (int64_t e = 0; e < g.E; e++) {
-        const int32_t a = g.eu[(size_t)e], b = g.ev[(size_t)e];
-        auto it = eidOf.find(key(a, b));
-        if (it != eidOf.end() && it->second < 0) it->second = (int32_t)e;
-        if (!g.directed) {
-            it = eidOf.find(key(b, a));
-            if (it != eidOf.end() && it->second < 0) it->second = (int32_t)e;
-        }
-    }
-    std::vector<int32_t> pe((size_t)n, -1);
-    for (int64_t i = 0; i < n; i++)
-        if (sv[(size_t)i] >= 0 && dv[(size_t)i] >= 0) pe[(size_t)i] = eidOf[key(sv[(size_t)i], dv[(size_t)i])];
-    return pe;
-}
-
-int64_t trace_complete(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
-                       int64_t n, ShdRoute* routes, int32_t* vertices, int32_t* edges, int64_t cap) {
-    const HostGraph& g = top->g;
-    const std::vector<int32_t> pe = complete_pair_eids(top, sv, dv, n);
-    std::vector<int32_t> eids((size_t)n, -1);
-    for (int64_t i = 0; i < n; i++) {
-        const int32_t s = sv[(size_t)i], d = dv[(size_t)i];
-        if (s < 0 || d < 0) {
-            routes[i] = route_blank(kTraceUnattached);
-            continue;
-        }
-        const int32_t e = pe[(size_t)i];
-        if (e < 0) {  // igraph_get_eid fails (shd-topology.c:857)
-            routes[i] = route_blank(kTraceBroken);
-            continue;
-        }
-        eids[(size_t)i] = e;
-        double rel = 1.0;
-        rel *= (1.0 - g.vloss[(size_t)s]);
-        rel *= (1.0 - g.vloss[(size_t)d]);
-        double lat = 0.0;
-        lat += g.elat[(size_t)e];
-        rel *= (1.0 - g.eloss[(size_t)e]);
-        routes[i].offset = -1;
-        routes[i].hops = 1;
-        routes[i].status = kTraceOk;
-        routes[i].latency = lat;
-        routes[i].reliability = rel;
-    }
-    const int64_t total = place_routes_host(routes, n, cap);
-    for (int64_t i = 0; i < n; i++) {
-        const int64_t o = routes[i].offset;
-        if (routes[i].status != kTraceOk || o < 0) continue;
-        vertices[o] = sv[(size_t)i];
-        vertices[o + 1] = dv[(size_t)i];
-        edges[o] = eids[(size_t)i];
-        edges[o + 1] = -1;
-    }
-    return total;
-}
-
-// ids of the replay CSR's vertices and entries (TraceIds), once per topology: at C4 the edge ids
-// are 80 MB, so the first trace uploads them, not the build.  Caller holds buildMu; the replay
-// CSR is uploaded.
-int ensure_trace_ids(Topology* top, double* ms) {
-    if (top->traceIdsReady) return 0;
-    const auto t0 = std::chrono::steady_clock::now();
-    const HostGraph& g = top->g;
-    const size_t V = (size_t)g.V;
-    hipStream_t st = top->stream;
-    HIPCHK(top->d_tperm.ensure(V));
-    HIPCHK(hipMemcpy(top->d_tperm.p, top->hp->perm.data(), 4 * V, hipMemcpyHostToDevice));
-    std::vector<int32_t> se(V, -1);  // lowest-id self loop per relabelled vertex
-    for (int64_t e = 0; e < g.E; e++) {
-        if (g.eu[(size_t)e] != g.ev[(size_t)e]) continue;
-        int32_t& x = se[(size_t)top->hp->inv[(size_t)g.eu[(size_t)e]]];
-        if (x < 0) x = (int32_t)e;
-    }
-    HIPCHK(top->d_selfEid.ensure(V));
-    HIPCHK(hipMemcpy(top->d_selfEid.p, se.data(), 4 * V, hipMemcpyHostToDevice));
-    HIPCHK(top->d_reid.ensure((size_t)std::max<int64_t>(1, top->rnadj)));
-    HIPCHK(launch_trace_edge_ids(g.V, g.E, top->isDirected ? 1 : 0, top->d_eu.p, top->d_ev.p,
-                                 top->d_inv.p, top->d_tperm.p, top->d_rrow.p, top->d_rrec.p,
-                                 top->rnadj, top->d_reid.p, st));
-    HIPCHK(hipStreamSynchronize(st));
-    top->traceIdsReady = true;
-    *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return 0;
-}
-
-// a trace leaves the last build's statistics and the replay's launch width as they were
-struct TraceKeep {
-    Topology* top;
-    ShdStats stats;
-    int rslotsUse;
-    explicit TraceKeep(Topology* t) : top(t), stats(t->stats), rslotsUse(t->rslotsUse) {}
-    ~TraceKeep() {
-        top->stats = stats;
-        top->rslotsUse = rslotsUse;
-    }
-};
-struct TraceEvents {
-    // 0 / 1 bracket a chunk's replay launch, 2 closes the chunk; 3 / 4 bracket its keep launch,
-    // 5 / 6 the pair walks' first pass
-    hipEvent_t e[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~TraceEvents() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
-
-// The requests of a trace or a link load grouped for the replay: those with both ends attached,
-// sorted by source (stable: request order within a source), a CSR over the distinct sources and
-// each source's slot within its chunk, uploaded; the replay's CSR and workspace for the table
-// build's target set; the events that time a chunk.
-struct ReplayReqs {
-    std::unique_ptr<TraceKeep> keep;  // declared first: ShdStats and the launch width go back last
-    std::vector<uint32_t> order, srcs, srcStart;
-    size_t nv = 0, mmax = 0;  // grouped requests; the most of one chunk
-    int nsrc = 0, chunk = 0;
-    ReplayCSR csr;
-    ReplayWs ws;
-    TraceIds ids;
-    DevBuf<uint32_t> d_srcs, d_rslot, d_rsrc, d_rdst, d_ridx;
-    DevBuf<unsigned long long> d_st;  // its own counters: the last build's stay intact
-    TraceEvents ev;
-    // The batch path (option "trace_batch", prepare_batch_path): a chunk's sources first run the
-    // batch kernel's keep launch, kf per batch and slot; the sources whose row it leaves
-    // unflagged are walked from the slots' pair records, the others replayed.  Everything the
-    // launch writes besides the batch workspace is the call's: targets, shifts, row flags, stats.
-    bool batchOk = false;
-    int K = 0, kf = 0;
-    double delta = 0.0;
-    SsspLdsPlan plan;
-    DevCSR bcsr;
-    SlotWs bws;
-    PairChains pc;
-    DevBuf<uint32_t> d_tgt, d_rmap, d_fsrcs;
-    DevBuf<double> d_srcsh, d_h0seed;
-    DevBuf<uint8_t> d_rowflag, d_broken;
-    DevBuf<unsigned long long> d_bst;
-    // one chunk's chains (chunk_chains): rmap[i] of chunk source i, the sources replayed
-    std::vector<uint32_t> rmap;
-    bool mixed = false;  // the chunk ran a keep launch: its requests carry rmap
-    int nfall = 0;       // sources of the chunk that were replayed
-    TraceReqs reqs(int s0, int s1) const {
-        TraceReqs rq;
-        const size_t q0 = srcStart[(size_t)s0];
-        rq.n = (int64_t)(srcStart[(size_t)s1] - q0);
-        rq.rslot = d_rslot.p + q0;
-        rq.rsrc = d_rsrc.p + q0;
-        rq.rdst = d_rdst.p + q0;
-        rq.ridx = d_ridx.p + q0;
-        return rq;
-    }
-};
-
-// Whether this call's chains may come from the batch kernel, and if so what its
-// keep launches need.  The launch must compute the rows a table build of the current attached set
-// would: the build's conditions for running the batch kernel at all (the allReplay rule of
-// enqueue_rows), its workspace, and a relaxation copy that is usable for the current target set
-// as it stands -- a trace neither prepares a target set nor restores the plain copy.  The tree
-// accumulation of a link load keeps its state in the replay's records (forLoadTree): replay.
-int prepare_batch_path(Topology* top, const std::vector<uint32_t>& tgt, bool forLoadTree,
-                       ReplayReqs& R) {
-    R.batchOk = false;
-    if (!top->traceBatch || top->isComplete || forLoadTree) return 0;
-    const bool dense = top->tieReplay && (top->tieDenseOpt == 1 ||
-                                          (top->tieDenseOpt < 0 && top->tieDense));
-    if (top->replayAll || top->hasMultiEdges || dense) return 0;
-    const bool leaf = leaf_targets_on(top);
-    const bool copyOk = top->adjkPlain ? !top->targetSkip
-                                       : top->adjkTargets == tgt && top->adjkLeaf == leaf;
-    if (!copyOk || !top->d_adjk.p || !top->d_adj.p) return 0;
-    const int K = batch_k(top);
-    const size_t hparN = (size_t)std::min<int64_t>(top->parHubs, 1 << 20) * K;
-    if (top->slots <= 0 || top->wsK != K || top->wsRing != ring_entries(top, K) ||
-        top->wsHpar < hparN || top->wsRsChunk != top->rsChunk) {
-        // no workspace of this layout (released, or never built here): the next build's
-        if (ensure_workspace(top, R.nsrc) != 0) {
-            (void)hipGetLastError();
-            return 0;
-        }
-        // the one thing of this call that ShdStats keeps: the workspace a later build will find
-        R.keep->stats.slots = top->stats.slots;
-        R.keep->stats.workspace_bytes = top->stats.workspace_bytes;
-        R.keep->stats.workspace_ms = top->stats.workspace_ms;
-    }
-    if (top->slots <= 0) return 0;
-    R.K = K;
-    const int fill = (int)top->stats.batch_fill;  // consecutive groups of the build's fill
-    R.kf = fill >= 1 && fill <= K ? fill : K;
-    R.delta = default_delta(top);
-    R.plan = batch_lds_plan(top, K);
-    R.bcsr = dev_csr(top);
-    R.bws = slot_ws(top);
-    R.pc.prec = R.bws.prec;
-    R.pc.counters = R.bws.counters;
-    R.pc.slots = R.bws.slots;
-    R.pc.K = K;
-    R.pc.kf = R.kf;
-    const int64_t A = (int64_t)tgt.size();
-    const std::vector<double> sh = source_shifts(top, R.srcs.data(), R.nsrc, R.delta);
-    HIPCHK(R.d_tgt.ensure((size_t)std::max<int64_t>(1, A)));
-    HIPCHK(R.d_srcsh.ensure((size_t)R.nsrc));
-    HIPCHK(R.d_bst.ensure(ST_COUNT));
-    HIPCHK(hipMemcpy(R.d_tgt.p, tgt.data(), 4 * (size_t)A, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(R.d_srcsh.p, sh.data(), 8 * (size_t)R.nsrc, hipMemcpyHostToDevice));
-    const std::vector<double> hs = source_h0_seeds(top, R.srcs.data(), R.nsrc);
-    HIPCHK(R.d_h0seed.ensure((size_t)R.nsrc));
-    HIPCHK(hipMemcpy(R.d_h0seed.p, hs.data(), 8 * (size_t)R.nsrc, hipMemcpyHostToDevice));
-    if (leaf) {  // the build's leaf-target records: the keep launch resolves the same targets so
-        const int r = ensure_leaf_targets(top, tgt, R.d_tgt.p, top->stream);
-        if (r) return r;
-        R.bws.tleaf = top->d_tleaf.p;
-    }
-    R.batchOk = true;
-    return 0;
-}
-
-// sv / dv: the requests' vertices (-1 = not attached).  Prepares the device, the replay and the
-// edge ids (*ids_ms), and fills R.  forLoadTree: a link load with the tree accumulation.
-int group_replay_requests(Topology* top, const std::vector<int32_t>& sv,
-                          const std::vector<int32_t>& dv, int64_t n, double* ids_ms,
-                          bool forLoadTree, ReplayReqs& R) {
-    int r = dev_init(top);
-    if (r) return r;
-    r = collect_row_stats(top);  // the last build's counters are read before the replay is reused
-    if (r) return r;
-    R.keep.reset(new TraceKeep(top));
-    r = upload_csr(top);
-    if (r) return r;
-    r = upload_replay(top);
-    if (r) return r;
-    r = ensure_trace_ids(top, ids_ms);
-    if (r) return r;
-    hipStream_t st = top->stream;
-    const std::vector<int32_t>& inv = top->hp->inv;
-
-    std::vector<uint32_t>& order = R.order;
-    for (int64_t i = 0; i < n; i++)
-        if (sv[(size_t)i] >= 0 && dv[(size_t)i] >= 0) order.push_back((uint32_t)i);
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-        return inv[(size_t)sv[a]] < inv[(size_t)sv[b]];
-    });
-    const size_t nv = R.nv = order.size();
-    std::vector<uint32_t>& srcs = R.srcs;
-    std::vector<uint32_t>& srcStart = R.srcStart;
-    std::vector<uint32_t> rsi(nv), rsrc(nv), rdst(nv);
-    for (size_t q = 0; q < nv; q++) {
-        const uint32_t s = (uint32_t)inv[(size_t)sv[order[q]]];
-        if (srcs.empty() || srcs.back() != s) {
-            srcs.push_back(s);
-            srcStart.push_back((uint32_t)q);
-        }
-        rsi[q] = (uint32_t)srcs.size() - 1u;
-        rsrc[q] = s;
-        rdst[q] = (uint32_t)inv[(size_t)dv[order[q]]];
-    }
-    srcStart.push_back((uint32_t)nv);
-    const int nsrc = R.nsrc = (int)srcs.size();
-
-    // the table build's target set: the chains are the table's chains
-    r = ensure_replay_ws(top, nsrc);
-    if (r) return r;
-    const int64_t A = top->A;
-    std::vector<uint32_t> tgt((size_t)A);
-    for (int64_t i = 0; i < A; i++) tgt[(size_t)i] = (uint32_t)inv[(size_t)top->attached[(size_t)i]];
-    r = upload_target_bits(top, tgt, st);
-    if (r) return r;
-    R.csr = replay_csr(top);
-    R.ws = replay_ws(top);
-    r = prepare_batch_path(top, tgt, forLoadTree, R);
-    if (r) return r;
-    // a chunk's sources fit the replay's slots and, on the batch path, one batch per batch slot
-    int chunk = R.ws.slots;
-    if (R.batchOk)
-        chunk = (int)std::min<int64_t>(chunk, (int64_t)R.bws.slots * R.kf);
-    if (top->traceChunk > 0) chunk = std::min(chunk, top->traceChunk);
-    if (chunk < 1) return -3;
-    R.chunk = chunk;
-    std::vector<uint32_t> rslot(nv);
-    for (size_t q = 0; q < nv; q++) rslot[q] = rsi[q] % (uint32_t)chunk;
-    for (int s0 = 0; s0 < nsrc; s0 += chunk)
-        R.mmax = std::max<size_t>(R.mmax, srcStart[(size_t)std::min(nsrc, s0 + chunk)] - srcStart[(size_t)s0]);
-
-    HIPCHK(R.d_srcs.ensure((size_t)nsrc));
-    HIPCHK(R.d_rslot.ensure(nv)); HIPCHK(R.d_rsrc.ensure(nv)); HIPCHK(R.d_rdst.ensure(nv));
-    HIPCHK(R.d_ridx.ensure(nv));
-    HIPCHK(R.d_st.ensure(ST_COUNT));
-    if (R.batchOk) {
-        HIPCHK(R.d_rmap.ensure((size_t)chunk));
-        HIPCHK(R.d_fsrcs.ensure((size_t)chunk));
-        HIPCHK(R.d_rowflag.ensure((size_t)chunk));
-        HIPCHK(R.d_broken.ensure((size_t)chunk));
-    }
-    HIPCHK(hipMemcpy(R.d_srcs.p, srcs.data(), 4 * (size_t)nsrc, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(R.d_rslot.p, rslot.data(), 4 * nv, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(R.d_rsrc.p, rsrc.data(), 4 * nv, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(R.d_rdst.p, rdst.data(), 4 * nv, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(R.d_ridx.p, order.data(), 4 * nv, hipMemcpyHostToDevice));
-    for (hipEvent_t& x : R.ev.e) HIPCHK(hipEventCreate(&x));
-    R.ids = TraceIds{top->d_tperm.p, top->d_reid.p, top->d_selfEid.p};
-    return 0;
-}
-
-// Sources [s0, s1) of R replayed in slots 0 .. s1 - s0 - 1 (the trace launch: the vertex records
-// stay for the walks); R.ev.e[0] and e[1] bracket the launch.
-int launch_replay_chunk(Topology* top, ReplayReqs& R, int s0, int s1) {
-    hipStream_t st = top->stream;
-    HIPCHK(hipMemsetAsync(R.d_st.p, 0, sizeof(unsigned long long) * ST_COUNT, st));
-    HIPCHK(hipEventRecord(R.ev.e[0], st));
-    HIPCHK(launch_heap_replay_trace(R.csr, R.ws, R.d_srcs.p + s0, s1 - s0, R.d_st.p, st));
-    HIPCHK(hipEventRecord(R.ev.e[1], st));
-    return 0;
-}
-
-// The chains of chunk [s0, s1) of R's sources, *rq its requests.  Without the batch path: the
-// replay of every source, as launch_replay_chunk.  With it:
-//   keep launch of the chunk's sources (ev 3 / 4), its row flags and ST_ERRORS read back;
-//   rmap: an unflagged source is served from its batch slot's pair records, a flagged one -- the
-//     rows a table build replays -- gets a replay slot;
-//   pairs1(rq, again): the caller's first pass over the pair records (the trace's count, the
-//     load's validation; ev 5 / 6), which marks the sources with a broken requested chain in
-//     R.d_broken.  Only a launch that counted errors can have one: then the marks are read, those
-//     sources join the replay list and pairs1 runs once more (again = true) without them;
-//   the replay of the listed sources in slots 0 .. nfall - 1 (ev 0 / 1).
-// On return rq carries rmap, R.nfall says how many sources were replayed (their first pass is
-// the caller's), and the times and counts are added to the three statistics.
-template <class F>
-int chunk_chains(Topology* top, ReplayReqs& R, int s0, int s1, TraceReqs* rq, F&& pairs1,
-                 double* batch_ms, int64_t* batch_sources, int64_t* batch_fallback) {
-    hipStream_t st = top->stream;
-    R.mixed = false;
-    if (!R.batchOk) {
-        R.nfall = s1 - s0;
-        return launch_replay_chunk(top, R, s0, s1);
-    }
-    const int ns = s1 - s0;
-    R.mixed = true;
-    HIPCHK(hipMemsetAsync(R.d_bst.p, 0, sizeof(unsigned long long) * ST_COUNT, st));
-    HIPCHK(hipMemsetAsync(R.d_rowflag.p, 0, (size_t)ns, st));
-    HIPCHK(hipMemsetAsync(R.d_broken.p, 0, (size_t)ns, st));
-    int r = hub_rows_ready(top, R.plan.H, st);
-    if (r) return r;
-    SlotWs ws = R.bws;
-    ws.rowflag = R.d_rowflag.p;
-    HIPCHK(hipEventRecord(R.ev.e[3], st));
-    HIPCHK(launch_sssp_batch_keep(R.K, R.bcsr, ws, R.d_srcs.p + s0, R.d_srcsh.p + s0,
-                                  R.d_h0seed.p + s0, ns, R.kf, R.d_tgt.p, (int)top->A, R.delta, R.plan, top->iterGuard,
-                                  R.d_bst.p, st));
-    HIPCHK(hipEventRecord(R.ev.e[4], st));
-    std::vector<uint8_t> fl((size_t)ns), br((size_t)ns, 0);
-    unsigned long long bst[ST_OVERFLOW + 1] = {};
-    HIPCHK(hipMemcpyAsync(fl.data(), R.d_rowflag.p, (size_t)ns, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(bst, R.d_bst.p, sizeof bst, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, R.ev.e[3], R.ev.e[4]));
-    *batch_ms += ms;
-    // a launch that overflowed a queue or tripped the iteration guard is not trusted: replay
-    const bool distrust = bst[ST_OVERFLOW] != 0;
-    std::vector<uint32_t> fsrc;
-    auto build_map = [&]() {
-        R.rmap.assign((size_t)ns, kNoReplaySlot);
-        fsrc.clear();
-        for (int i = 0; i < ns; i++)
-            if (distrust || fl[(size_t)i] || br[(size_t)i]) {
-                R.rmap[(size_t)i] = (uint32_t)fsrc.size();
-                fsrc.push_back(R.srcs[(size_t)(s0 + i)]);
-            }
-        return hipMemcpy(R.d_rmap.p, R.rmap.data(), 4 * (size_t)ns, hipMemcpyHostToDevice);
-    };
-    HIPCHK(build_map());
-    rq->rmap = R.d_rmap.p;
-    rq->nmap = (uint32_t)ns;
-    if ((int)fsrc.size() < ns) {
-        HIPCHK(hipEventRecord(R.ev.e[5], st));
-        r = pairs1(*rq, false);
-        if (r) return r;
-        if (bst[ST_ERRORS]) {
-            HIPCHK(hipMemcpyAsync(br.data(), R.d_broken.p, (size_t)ns, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            bool any = false;
-            for (int i = 0; i < ns; i++) any |= br[(size_t)i] != 0 && R.rmap[(size_t)i] == kNoReplaySlot;
-            if (any) {
-                HIPCHK(build_map());
-                r = pairs1(*rq, true);
-                if (r) return r;
-            }
-        }
-        HIPCHK(hipEventRecord(R.ev.e[6], st));
-    }
-    R.nfall = (int)fsrc.size();
-    *batch_sources += ns - R.nfall;
-    *batch_fallback += R.nfall;
-    HIPCHK(hipMemsetAsync(R.d_st.p, 0, sizeof(unsigned long long) * ST_COUNT, st));
-    HIPCHK(hipEventRecord(R.ev.e[0], st));
-    if (R.nfall > 0) {
-        HIPCHK(hipMemcpy(R.d_fsrcs.p, fsrc.data(), 4 * fsrc.size(), hipMemcpyHostToDevice));
-        HIPCHK(launch_heap_replay_trace(R.csr, R.ws, R.d_fsrcs.p, R.nfall, R.d_st.p, st));
-    }
-    HIPCHK(hipEventRecord(R.ev.e[1], st));
-    return 0;
-}
-// event times of a chunk after its closing event (ev 2) and a stream sync: the replay launch (if
-// one ran) and everything else but the keep launch
-int chunk_times(ReplayReqs& R, double* replay_ms, double* kernel_ms) {
-    float ms = 0;
-    if (R.nfall > 0) {
-        HIPCHK(hipEventElapsedTime(&ms, R.ev.e[0], R.ev.e[1]));
-        *replay_ms += ms;
-    }
-    HIPCHK(hipEventElapsedTime(&ms, R.ev.e[1], R.ev.e[2]));
-    *kernel_ms += ms;
-    if (R.mixed && R.nfall < (int)R.rmap.size()) {
-        HIPCHK(hipEventElapsedTime(&ms, R.ev.e[5], R.ev.e[6]));
-        *kernel_ms += ms;
-    }
-    return 0;
-}
-
-// SSSP topologies: the distinct sources in chunks -- chains from the batch kernel's pair records
-// or the replay (chunk_chains) -- and the walks of the requests' chains (topo_trace.hip)
-int64_t trace_replay(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
-                     int64_t n, ShdRoute* routes, int32_t* vertices, int32_t* edges, int64_t cap,
-                     ShdTraceStats* ts) {
-    ReplayReqs R;
-    int r = group_replay_requests(top, sv, dv, n, &ts->ids_ms, false, R);
-    if (r) return r;
-    hipStream_t st = top->stream;
-    const std::vector<uint32_t>& srcStart = R.srcStart;
-    const size_t nv = R.nv, mmax = R.mmax;
-    const int nsrc = R.nsrc, chunk = R.chunk;
-    const ReplayCSR& csr = R.csr;
-    const ReplayWs& ws = R.ws;
-    const TraceIds& ids = R.ids;
-    TraceEvents& ev = R.ev;
-    ts->sources = nsrc;
-
-    DevBuf<TraceRoute> d_routes;
-    DevBuf<int64_t> d_gneed, d_goff, d_lneed, d_coff, d_loff;
-    DevBuf<int32_t> d_outV, d_outE;
-    HIPCHK(d_routes.ensure((size_t)n));
-    HIPCHK(d_gneed.ensure((size_t)n + 1)); HIPCHK(d_goff.ensure((size_t)n + 1));
-    HIPCHK(d_lneed.ensure(mmax + 1)); HIPCHK(d_coff.ensure(mmax + 1)); HIPCHK(d_loff.ensure(nv));
-    // requests with an unattached end keep their host image; pass 1 writes the others
-    for (int64_t i = 0; i < n; i++) routes[i] = route_blank(kTraceUnattached);
-    HIPCHK(hipMemcpy(d_routes.p, routes, sizeof(ShdRoute) * (size_t)n, hipMemcpyHostToDevice));
-    HIPCHK(hipMemsetAsync(d_gneed.p, 0, 8 * ((size_t)n + 1), st));
-
-    auto reqs = [&](int s0, int s1) { return R.reqs(s0, s1); };
-    std::vector<std::unique_ptr<DevBuf<int32_t>>> stage;  // per chunk: vertices, edges
-    float ms = 0;
-    for (int s0 = 0; s0 < nsrc; s0 += chunk) {
-        const int s1 = std::min(nsrc, s0 + chunk);
-        TraceReqs rq = reqs(s0, s1);
-        const size_t q0 = srcStart[(size_t)s0], m = (size_t)rq.n;
-        HIPCHK(hipMemsetAsync(d_lneed.p, 0, 8 * (m + 1), st));
-        // both chain sources write the same routes, needs and staging: each takes its requests
-        r = chunk_chains(top, R, s0, s1, &rq,
-                         [&](const TraceReqs& q, bool) {
-                             HIPCHK(launch_route_trace_count_pairs(csr, R.pc, q, d_routes.p, d_lneed.p,
-                                                                   d_gneed.p, R.d_broken.p, st));
-                             return 0;
-                         },
-                         &ts->batch_ms, &ts->batch_sources, &ts->batch_fallback);
-        if (r) return r;
-        if (R.nfall > 0)
-            HIPCHK(launch_route_trace_count(csr, ws, rq, d_routes.p, d_lneed.p, d_gneed.p, st));
-        HIPCHK(trace_exclusive_scan(d_lneed.p, d_coff.p, (int64_t)m + 1, st));
-        int64_t tot = 0;
-        HIPCHK(hipMemcpy(&tot, d_coff.p + m, 8, hipMemcpyDeviceToHost));
-        stage.emplace_back(new DevBuf<int32_t>());
-        stage.emplace_back(new DevBuf<int32_t>());
-        DevBuf<int32_t>& stV = *stage[stage.size() - 2];
-        DevBuf<int32_t>& stE = *stage[stage.size() - 1];
-        HIPCHK(stV.ensure((size_t)std::max<int64_t>(1, tot)));
-        HIPCHK(stE.ensure((size_t)std::max<int64_t>(1, tot)));
-        if (R.mixed && R.nfall < s1 - s0)
-            HIPCHK(launch_route_trace_write_pairs(csr, R.pc, ids, rq, d_routes.p, d_coff.p, stV.p,
-                                                  stE.p, st));
-        if (R.nfall > 0)
-            HIPCHK(launch_route_trace_write(csr, ws, ids, rq, d_routes.p, d_coff.p, stV.p, stE.p, st));
-        HIPCHK(hipMemcpyAsync(d_loff.p + q0, d_coff.p, 8 * m, hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipEventRecord(ev.e[2], st));
-        HIPCHK(hipStreamSynchronize(st));
-        r = chunk_times(R, &ts->replay_ms, &ts->trace_kernel_ms);
-        if (r) return r;
-        ts->chunks++;
-    }
-
-    // the call's offsets: exclusive scan in request order, then the routes that fit are copied out
-    HIPCHK(hipEventRecord(ev.e[0], st));
-    HIPCHK(trace_exclusive_scan(d_gneed.p, d_goff.p, n + 1, st));
-    HIPCHK(launch_route_trace_place(n, d_routes.p, d_goff.p, cap, st));
-    int64_t total = 0;
-    HIPCHK(hipMemcpyAsync(&total, d_goff.p + n, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(routes, d_routes.p, sizeof(ShdRoute) * (size_t)n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    int64_t fit = 0;  // the placed routes fill [0, fit): offsets are a running sum
-    for (int64_t i = 0; i < n; i++)
-        if (routes[i].status == kTraceOk && routes[i].offset >= 0)
-            fit = std::max(fit, routes[i].offset + routes[i].hops + 1);
-    if (fit > cap) return -3;
-    if (fit > 0) {
-        HIPCHK(d_outV.ensure((size_t)fit));
-        HIPCHK(d_outE.ensure((size_t)fit));
-        size_t c = 0;
-        for (int s0 = 0; s0 < nsrc; s0 += chunk, c += 2)
-            HIPCHK(launch_route_trace_scatter(reqs(s0, std::min(nsrc, s0 + chunk)), d_routes.p,
-                                              d_loff.p + srcStart[(size_t)s0], stage[c]->p,
-                                              stage[c + 1]->p, d_outV.p, d_outE.p, st));
-    }
-    HIPCHK(hipEventRecord(ev.e[1], st));
-    if (fit > 0) {
-        HIPCHK(hipMemcpyAsync(vertices, d_outV.p, 4 * (size_t)fit, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(edges, d_outE.p, 4 * (size_t)fit, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-    ts->trace_kernel_ms += ms;
-    return total;
-}
-
-// ---------------------------------------------------------------------------------------------
-// link load (include/shd_topology_abi.h shdtopo_link_load; kernels in topo_load.hip)
-// ---------------------------------------------------------------------------------------------
-// Complete topologies, on the host as trace_complete: one hop over the direct edge, a self pair
-// over the loop.
-int64_t load_complete(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
-                      const uint64_t* weight, int64_t n, uint64_t* edgeLoad, uint64_t* vertexLoad,
-                      ShdLoadStats* ls) {
-    const HostGraph& g = top->g;
-    const std::vector<int32_t> pe = complete_pair_eids(top, sv, dv, n);
-    for (int64_t i = 0; i < n; i++) {
-        const int32_t s = sv[(size_t)i], d = dv[(size_t)i];
-        if (s < 0 || d < 0) continue;  // counted by the caller
-        const int32_t e = pe[(size_t)i];
-        if (e < 0) {
-            ls->broken++;
-            continue;
-        }
-        const uint64_t w = weight ? weight[i] : 1;
-        if (edgeLoad) edgeLoad[s == g.eu[(size_t)e] ? (int64_t)e : g.E + e] += w;
-        if (vertexLoad) vertexLoad[d] += w;
-        ls->routed++;
-        ls->hop_weight += w;
-    }
-    return ls->routed;
-}
-
-// SSSP topologies: the distinct sources in chunks -- chains from the batch kernel's pair records
-// (the per-request walk only) or the replay (chunk_chains) -- and the sums along the chains
-int64_t load_replay(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
-                    const uint64_t* weight, int64_t n, uint64_t* edgeLoad, uint64_t* vertexLoad,
-                    ShdLoadStats* ls) {
-    ReplayReqs R;
-    int r = group_replay_requests(top, sv, dv, n, &ls->ids_ms, !top->loadWalk, R);
-    if (r) return r;
-    hipStream_t st = top->stream;
-    const size_t nv = R.nv, V = (size_t)top->g.V, E = (size_t)top->g.E;
-    ls->sources = R.nsrc;
-
-    std::vector<unsigned long long> rw(nv, 1ull);
-    if (weight)
-        for (size_t q = 0; q < nv; q++) rw[q] = weight[R.order[q]];
-    DevBuf<unsigned long long> d_w, d_eload, d_vload, d_vout, d_cnt, d_pcnt;
-    DevBuf<int32_t> d_hops;
-    HIPCHK(d_w.ensure(nv));
-    HIPCHK(d_hops.ensure(nv));
-    HIPCHK(d_eload.ensure(2 * E));
-    HIPCHK(d_vload.ensure(V));
-    HIPCHK(d_vout.ensure(V));
-    HIPCHK(d_cnt.ensure(LD_COUNT));
-    HIPCHK(d_pcnt.ensure(LD_COUNT));
-    HIPCHK(hipMemcpy(d_w.p, rw.data(), 8 * nv, hipMemcpyHostToDevice));
-    HIPCHK(hipMemsetAsync(d_eload.p, 0, 8 * std::max<size_t>(1, 2 * E), st));
-    HIPCHK(hipMemsetAsync(d_vload.p, 0, 8 * std::max<size_t>(1, V), st));
-    HIPCHK(hipMemsetAsync(d_vout.p, 0, 8 * std::max<size_t>(1, V), st));
-    HIPCHK(hipMemsetAsync(d_cnt.p, 0, 8 * LD_COUNT, st));
-    LoadAcc acc;
-    acc.eload = d_eload.p;
-    acc.vload = d_vload.p;
-    acc.E = (int64_t)E;
-    acc.eu = top->d_eu.p;
-
-    float ms = 0;
-    // counters of the pair walks' validation: per chunk in d_pcnt (a validation that finds a
-    // broken chain is run again without that source), summed here
-    unsigned long long pcnt[LD_COUNT] = {};
-    for (int s0 = 0; s0 < R.nsrc; s0 += R.chunk) {
-        const int s1 = std::min(R.nsrc, s0 + R.chunk);
-        TraceReqs rq = R.reqs(s0, s1);
-        const size_t q0 = R.srcStart[(size_t)s0];
-        r = chunk_chains(top, R, s0, s1, &rq,
-                         [&](const TraceReqs& q, bool) {
-                             HIPCHK(hipMemsetAsync(d_pcnt.p, 0, 8 * LD_COUNT, st));
-                             HIPCHK(launch_load_validate_pairs(R.csr, R.pc, q, d_w.p + q0,
-                                                               d_hops.p + q0, d_pcnt.p,
-                                                               R.d_broken.p, st));
-                             return 0;
-                         },
-                         &ls->batch_ms, &ls->batch_sources, &ls->batch_fallback);
-        if (r) return r;
-        const bool pairs = R.mixed && R.nfall < s1 - s0;
-        unsigned long long c[LD_COUNT] = {};
-        if (pairs) {
-            HIPCHK(hipMemcpyAsync(c, d_pcnt.p, 8 * LD_COUNT, hipMemcpyDeviceToHost, st));
-            HIPCHK(launch_load_walk_pairs(R.csr, R.pc, R.ids, rq, d_w.p + q0, d_hops.p + q0, acc, st));
-        }
-        if (R.nfall > 0)
-            HIPCHK(launch_load_validate(R.csr, R.ws, rq, d_w.p + q0, d_hops.p + q0, d_cnt.p, st));
-        if (R.nfall > 0 && top->loadWalk) {
-            HIPCHK(launch_load_walk(R.csr, R.ws, R.ids, rq, d_w.p + q0, d_hops.p + q0, acc, st));
-        } else if (R.nfall > 0) {
-            HIPCHK(launch_load_reset(R.csr, R.ws, s1 - s0, st));
-            HIPCHK(launch_load_claim(R.csr, R.ws, R.ids, rq, d_w.p + q0, d_hops.p + q0, acc,
-                                     d_cnt.p, st));
-            HIPCHK(launch_load_push(R.csr, R.ws, R.ids, rq, d_hops.p + q0, acc, st));
-        }
-        HIPCHK(hipEventRecord(R.ev.e[2], st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int i = 0; i < LD_COUNT; i++) pcnt[i] += c[i];
-        r = chunk_times(R, &ls->replay_ms, &ls->load_kernel_ms);
-        if (r) return r;
-        ls->chunks++;
-    }
-
-    HIPCHK(hipEventRecord(R.ev.e[0], st));
-    HIPCHK(launch_load_permute((int64_t)V, R.ids.perm, d_vload.p, d_vout.p, st));
-    HIPCHK(hipEventRecord(R.ev.e[1], st));
-    unsigned long long cnt[LD_COUNT] = {};
-    HIPCHK(hipMemcpyAsync(cnt, d_cnt.p, 8 * LD_COUNT, hipMemcpyDeviceToHost, st));
-    if (edgeLoad && E) HIPCHK(hipMemcpyAsync(edgeLoad, d_eload.p, 8 * 2 * E, hipMemcpyDeviceToHost, st));
-    if (vertexLoad && V) HIPCHK(hipMemcpyAsync(vertexLoad, d_vout.p, 8 * V, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipEventElapsedTime(&ms, R.ev.e[0], R.ev.e[1]));
-    ls->load_kernel_ms += ms;
-    for (int i = 0; i < LD_COUNT; i++) cnt[i] += pcnt[i];
-    ls->routed = (int64_t)cnt[LD_ROUTED];
-    ls->broken = (int64_t)cnt[LD_BROKEN];
-    ls->hop_weight = cnt[LD_HOPW];
-    ls->tree_vertices = (int64_t)cnt[LD_TREE];
-    return ls->routed;
-}
-
-// ---------------------------------------------------------------------------------------------
-// link crossings (include/shd_topology_abi.h shdtopo_link_crossings; kernels in topo_cross.hip)
-// ---------------------------------------------------------------------------------------------
-static_assert(sizeof(ShdCrossing) == 16 && sizeof(CrossRec) == sizeof(ShdCrossing) &&
-                  offsetof(ShdCrossing, flow) == offsetof(CrossRec, flow) &&
-                  offsetof(ShdCrossing, watch) == offsetof(CrossRec, watch) &&
-                  offsetof(ShdCrossing, hop) == offsetof(CrossRec, hop) &&
-                  offsetof(ShdCrossing, reverse) == offsetof(CrossRec, reverse),
-              "CrossRec is the device image of ShdCrossing");
-
-// The watch set of one call: the ids of each list ascending with their watch index (edges k,
-// vertices ne + k; original vertex ids).  false: an id out of range or twice in its list.
-struct WatchSet {
-    std::vector<int32_t> eids, eidx, vids, vidx;
-    static bool sorted_ids(const int32_t* id, int64_t n, int64_t limit, int32_t idx0,
-                           std::vector<int32_t>& ids, std::vector<int32_t>& idx) {
-        std::vector<std::pair<int32_t, int32_t>> s((size_t)n);
-        for (int64_t k = 0; k < n; k++) {
-            if (id[k] < 0 || (int64_t)id[k] >= limit) return false;
-            s[(size_t)k] = {id[k], (int32_t)(idx0 + k)};
-        }
-        std::sort(s.begin(), s.end());
-        ids.resize((size_t)n);
-        idx.resize((size_t)n);
-        for (size_t k = 0; k < (size_t)n; k++) {
-            if (k > 0 && s[k].first == s[k - 1].first) return false;
-            ids[k] = s[k].first;
-            idx[k] = s[k].second;
-        }
-        return true;
-    }
-    bool init(const HostGraph& g, const int32_t* we, int64_t ne, const int32_t* wv, int64_t nv) {
-        return sorted_ids(we, ne, g.E, 0, eids, eidx) &&
-               sorted_ids(wv, nv, g.V, (int32_t)ne, vids, vidx);
-    }
-    static int32_t find(const std::vector<int32_t>& ids, const std::vector<int32_t>& idx,
-                        int32_t x) {
-        const auto it = std::lower_bound(ids.begin(), ids.end(), x);
-        return it != ids.end() && *it == x ? idx[(size_t)(it - ids.begin())] : -1;
-    }
-    int32_t edge(int32_t e) const { return find(eids, eidx, e); }
-    int32_t vertex(int32_t v) const { return find(vids, vidx, v); }
-};
-
-// The device image of a watch set (CrossWatch, its totals aside): bits by edge id and by
-// relabelled vertex, the sorted ids for the hits.
-struct DevWatch {
-    DevBuf<uint32_t> d_ebits, d_vbits;
-    DevBuf<int32_t> d_eids, d_eidx, d_vids, d_vidx;
-    CrossWatch cw;
-    int upload(Topology* top, const WatchSet& wset) {
-        const size_t V = (size_t)top->g.V, E = (size_t)top->g.E;
-        const size_t ne = wset.eids.size(), nvw = wset.vids.size();
-        std::vector<uint32_t> ebits(E / 32 + 1, 0u), vbits(V / 32 + 1, 0u);
-        for (int32_t e : wset.eids) ebits[(size_t)e >> 5] |= 1u << (e & 31);
-        std::vector<std::pair<int32_t, int32_t>> rv(nvw);
-        for (size_t k = 0; k < nvw; k++) {
-            const int32_t x = top->hp->inv[(size_t)wset.vids[k]];
-            vbits[(size_t)x >> 5] |= 1u << (x & 31);
-            rv[k] = {x, wset.vidx[k]};
-        }
-        std::sort(rv.begin(), rv.end());
-        std::vector<int32_t> vids(nvw), vidx(nvw);
-        for (size_t k = 0; k < nvw; k++) {
-            vids[k] = rv[k].first;
-            vidx[k] = rv[k].second;
-        }
-        HIPCHK(d_ebits.ensure(ebits.size())); HIPCHK(d_vbits.ensure(vbits.size()));
-        HIPCHK(d_eids.ensure(std::max<size_t>(1, ne))); HIPCHK(d_eidx.ensure(std::max<size_t>(1, ne)));
-        HIPCHK(d_vids.ensure(std::max<size_t>(1, nvw))); HIPCHK(d_vidx.ensure(std::max<size_t>(1, nvw)));
-        HIPCHK(hipMemcpy(d_ebits.p, ebits.data(), 4 * ebits.size(), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_vbits.p, vbits.data(), 4 * vbits.size(), hipMemcpyHostToDevice));
-        if (ne) {
-            HIPCHK(hipMemcpy(d_eids.p, wset.eids.data(), 4 * ne, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(d_eidx.p, wset.eidx.data(), 4 * ne, hipMemcpyHostToDevice));
-        }
-        if (nvw) {
-            HIPCHK(hipMemcpy(d_vids.p, vids.data(), 4 * nvw, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(d_vidx.p, vidx.data(), 4 * nvw, hipMemcpyHostToDevice));
-        }
-        cw.ebits = d_ebits.p;
-        cw.vbits = d_vbits.p;
-        cw.eids = d_eids.p;
-        cw.eidx = d_eidx.p;
-        cw.vids = d_vids.p;
-        cw.vidx = d_vidx.p;
-        cw.ne = (int32_t)ne;
-        cw.nv = (int32_t)nvw;
-        cw.E = (int64_t)E;
-        cw.eu = top->d_eu.p;
-        return 0;
-    }
-};
-
-// Complete topologies, on the host as load_complete: one hop (hop 0) over the direct edge, a self
-// pair over the loop; the edge record before the vertex record.
-int64_t cross_complete(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
-                       const uint64_t* weight, int64_t n, const WatchSet& ws, int64_t* flowOffset,
-                       ShdCrossing* out, int64_t cap, uint64_t* watchCount, uint64_t* watchWeight,
-                       ShdCrossStats* cs) {
-    const HostGraph& g = top->g;
-    const std::vector<int32_t> pe = complete_pair_eids(top, sv, dv, n);
-    int64_t off = 0;
-    for (int64_t i = 0; i < n; i++) {
-        if (flowOffset) flowOffset[i] = off;
-        const int32_t s = sv[(size_t)i], d = dv[(size_t)i];
-        if (s < 0 || d < 0) continue;  // counted by the caller
-        const int32_t e = pe[(size_t)i];
-        if (e < 0) {
-            cs->broken++;
-            continue;
-        }
-        cs->routed++;
-        const uint64_t w = weight ? weight[i] : 1;
-        ShdCrossing rec[2];
-        int m = 0;
-        const int32_t ke = ws.edge(e), kv = ws.vertex(d);
-        if (ke >= 0) rec[m++] = ShdCrossing{(int32_t)i, ke, 0, s != g.eu[(size_t)e] ? 1 : 0};
-        if (kv >= 0) rec[m++] = ShdCrossing{(int32_t)i, kv, 0, 0};
-        for (int k = 0; k < m; k++) {
-            if (watchCount) watchCount[rec[k].watch]++;
-            if (watchWeight) watchWeight[rec[k].watch] += w;
-            if (off + m <= cap) out[off + k] = rec[k];
-        }
-        if (m > 0) cs->flows_hit++;
-        off += m;
-    }
-    if (flowOffset) flowOffset[n] = off;
-    return off;
-}
-
-// SSSP topologies: the distinct sources in chunks -- chains from the batch kernel's pair records
-// or the replay (chunk_chains), whatever "load_walk" says -- link load's validation, then the
-// count and write walks of topo_cross.hip; the records are staged per chunk and placed once the
-// last chunk is walked (the structure of trace_replay)
-int64_t cross_replay(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
-                     const uint64_t* weight, int64_t n, const WatchSet& wset, int64_t* flowOffset,
-                     ShdCrossing* out, int64_t cap, uint64_t* watchCount, uint64_t* watchWeight,
-                     ShdCrossStats* cs) {
-    ReplayReqs R;
-    int r = group_replay_requests(top, sv, dv, n, &cs->ids_ms, false, R);
-    if (r) return r;
-    hipStream_t st = top->stream;
-    const size_t nv = R.nv, mmax = R.mmax;
-    const size_t ne = wset.eids.size(), nvw = wset.vids.size(), nw = ne + nvw;
-    cs->sources = R.nsrc;
-
-    DevWatch dw;
-    r = dw.upload(top, wset);
-    if (r) return r;
-    DevBuf<int32_t> d_hops;
-    DevBuf<unsigned long long> d_w, d_wcount, d_wweight, d_cnt, d_pcnt, d_ccnt;
-    DevBuf<int64_t> d_gcnt, d_goff, d_lcnt, d_coff, d_loff;
-    HIPCHK(d_wcount.ensure(nw)); HIPCHK(d_wweight.ensure(nw));
-    HIPCHK(hipMemsetAsync(d_wcount.p, 0, 8 * nw, st));
-    HIPCHK(hipMemsetAsync(d_wweight.p, 0, 8 * nw, st));
-    CrossWatch cw = dw.cw;
-    cw.wcount = d_wcount.p;
-    cw.wweight = d_wweight.p;
-
-    std::vector<unsigned long long> rw(nv, 1ull);
-    if (weight)
-        for (size_t q = 0; q < nv; q++) rw[q] = weight[R.order[q]];
-    HIPCHK(d_w.ensure(nv));
-    HIPCHK(d_hops.ensure(nv));
-    HIPCHK(d_cnt.ensure(LD_COUNT)); HIPCHK(d_pcnt.ensure(LD_COUNT)); HIPCHK(d_ccnt.ensure(CR_COUNT));
-    HIPCHK(d_gcnt.ensure((size_t)n + 1)); HIPCHK(d_goff.ensure((size_t)n + 1));
-    HIPCHK(d_lcnt.ensure(mmax + 1)); HIPCHK(d_coff.ensure(mmax + 1)); HIPCHK(d_loff.ensure(nv));
-    HIPCHK(hipMemcpy(d_w.p, rw.data(), 8 * nv, hipMemcpyHostToDevice));
-    HIPCHK(hipMemsetAsync(d_cnt.p, 0, 8 * LD_COUNT, st));
-    HIPCHK(hipMemsetAsync(d_ccnt.p, 0, 8 * CR_COUNT, st));
-    // requests with an unattached end have no records; the count pass writes the others
-    HIPCHK(hipMemsetAsync(d_gcnt.p, 0, 8 * ((size_t)n + 1), st));
-
-    std::vector<std::unique_ptr<DevBuf<CrossRec>>> stage;  // per chunk
-    float ms = 0;
-    unsigned long long pcnt[LD_COUNT] = {};  // the pair walks' validation, as load_replay
-    for (int s0 = 0; s0 < R.nsrc; s0 += R.chunk) {
-        const int s1 = std::min(R.nsrc, s0 + R.chunk);
-        TraceReqs rq = R.reqs(s0, s1);
-        const size_t q0 = R.srcStart[(size_t)s0], m = (size_t)rq.n;
-        HIPCHK(hipMemsetAsync(d_lcnt.p, 0, 8 * (m + 1), st));
-        r = chunk_chains(top, R, s0, s1, &rq,
-                         [&](const TraceReqs& q, bool) {
-                             HIPCHK(hipMemsetAsync(d_pcnt.p, 0, 8 * LD_COUNT, st));
-                             HIPCHK(launch_load_validate_pairs(R.csr, R.pc, q, d_w.p + q0,
-                                                               d_hops.p + q0, d_pcnt.p,
-                                                               R.d_broken.p, st));
-                             return 0;
-                         },
-                         &cs->batch_ms, &cs->batch_sources, &cs->batch_fallback);
-        if (r) return r;
-        // both chain sources write the same counts and staging: each takes its requests
-        const bool pairs = R.mixed && R.nfall < s1 - s0;
-        unsigned long long c[LD_COUNT] = {};
-        if (pairs) {
-            HIPCHK(hipMemcpyAsync(c, d_pcnt.p, 8 * LD_COUNT, hipMemcpyDeviceToHost, st));
-            HIPCHK(launch_cross_count_pairs(R.csr, R.pc, R.ids, rq, d_w.p + q0, d_hops.p + q0, cw,
-                                            d_lcnt.p, d_gcnt.p, d_ccnt.p, st));
-        }
-        if (R.nfall > 0) {
-            HIPCHK(launch_load_validate(R.csr, R.ws, rq, d_w.p + q0, d_hops.p + q0, d_cnt.p, st));
-            HIPCHK(launch_cross_count(R.csr, R.ws, R.ids, rq, d_w.p + q0, d_hops.p + q0, cw,
-                                      d_lcnt.p, d_gcnt.p, d_ccnt.p, st));
-        }
-        HIPCHK(trace_exclusive_scan(d_lcnt.p, d_coff.p, (int64_t)m + 1, st));
-        int64_t tot = 0;
-        HIPCHK(hipMemcpy(&tot, d_coff.p + m, 8, hipMemcpyDeviceToHost));
-        stage.emplace_back(new DevBuf<CrossRec>());
-        DevBuf<CrossRec>& stg = *stage.back();
-        HIPCHK(stg.ensure((size_t)std::max<int64_t>(1, tot)));
-        if (pairs && tot > 0)
-            HIPCHK(launch_cross_write_pairs(R.csr, R.pc, R.ids, rq, d_hops.p + q0, cw, d_coff.p,
-                                            stg.p, st));
-        if (R.nfall > 0 && tot > 0)
-            HIPCHK(launch_cross_write(R.csr, R.ws, R.ids, rq, d_hops.p + q0, cw, d_coff.p, stg.p, st));
-        HIPCHK(hipMemcpyAsync(d_loff.p + q0, d_coff.p, 8 * m, hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipEventRecord(R.ev.e[2], st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int i = 0; i < LD_COUNT; i++) pcnt[i] += c[i];
-        r = chunk_times(R, &cs->replay_ms, &cs->kernel_ms);
-        if (r) return r;
-        cs->chunks++;
-    }
-
-    // the call's offsets: exclusive scan in request order, then the flows that fit are copied out
-    HIPCHK(hipEventRecord(R.ev.e[0], st));
-    HIPCHK(trace_exclusive_scan(d_gcnt.p, d_goff.p, n + 1, st));
-    std::vector<int64_t> goff((size_t)n + 1);
-    HIPCHK(hipMemcpy(goff.data(), d_goff.p, 8 * ((size_t)n + 1), hipMemcpyDeviceToHost));
-    const int64_t total = goff[(size_t)n];
-    // offsets ascend: the flows written are those ending at or below cap, and fill [0, fit)
-    const int64_t fit =
-        *(std::upper_bound(goff.begin(), goff.end(), std::min(cap, total)) - 1);
-    DevBuf<CrossRec> d_out;
-    if (fit > 0) {
-        HIPCHK(d_out.ensure((size_t)fit));
-        size_t c = 0;
-        for (int s0 = 0; s0 < R.nsrc; s0 += R.chunk, c++)
-            HIPCHK(launch_cross_scatter(R.reqs(s0, std::min(R.nsrc, s0 + R.chunk)), d_goff.p,
-                                        d_loff.p + R.srcStart[(size_t)s0], stage[c]->p, d_out.p,
-                                        fit, st));
-    }
-    HIPCHK(hipEventRecord(R.ev.e[1], st));
-    unsigned long long cnt[LD_COUNT] = {}, ccnt[CR_COUNT] = {};
-    HIPCHK(hipMemcpyAsync(cnt, d_cnt.p, 8 * LD_COUNT, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(ccnt, d_ccnt.p, 8 * CR_COUNT, hipMemcpyDeviceToHost, st));
-    if (fit > 0)
-        HIPCHK(hipMemcpyAsync(out, d_out.p, sizeof(ShdCrossing) * (size_t)fit, hipMemcpyDeviceToHost, st));
-    if (watchCount && nw)
-        HIPCHK(hipMemcpyAsync(watchCount, d_wcount.p, 8 * nw, hipMemcpyDeviceToHost, st));
-    if (watchWeight && nw)
-        HIPCHK(hipMemcpyAsync(watchWeight, d_wweight.p, 8 * nw, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipEventElapsedTime(&ms, R.ev.e[0], R.ev.e[1]));
-    cs->kernel_ms += ms;
-    if (flowOffset) std::copy(goff.begin(), goff.end(), flowOffset);
-    cs->routed = (int64_t)(cnt[LD_ROUTED] + pcnt[LD_ROUTED]);
-    cs->broken = (int64_t)(cnt[LD_BROKEN] + pcnt[LD_BROKEN]);
-    cs->flows_hit = (int64_t)ccnt[CR_FLOWS];
-    if ((int64_t)ccnt[CR_RECORDS] != total) return -3;
-    return total;
-}
-
-// ---------------------------------------------------------------------------------------------
-// link timeline (include/shd_topology_abi.h shdtopo_link_timeline; kernels in topo_timeline.hip)
-// ---------------------------------------------------------------------------------------------
-// the packet kernel's conversion (topo_kernels.hip): milliseconds -> nanoseconds, rounded up
-uint64_t lat_ns(double ms) { return (uint64_t)std::ceil(ms * 1000000.0); }
-
-// where a hit lands, and its count
-struct TimelineOut {
-    uint64_t t0, binNs;
-    int64_t nbins;
-    uint64_t* bins;
-    uint64_t* outside;
-    void add(int64_t row, uint64_t t, uint64_t w, ShdTimelineStats* ts) const {
-        ts->hits++;
-        if (t < t0) {
-            ts->before++;
-            if (outside) outside[2 * row] += w;
-            return;
-        }
-        if (nbins > 0 && (t - t0) / binNs < (uint64_t)nbins) {
-            ts->in_range++;
-            bins[row * nbins + (int64_t)((t - t0) / binNs)] += w;
-            return;
-        }
-        ts->after++;
-        if (outside) outside[2 * row + 1] += w;
-    }
-};
-
-// Complete topologies, on the host as cross_complete: one hop over the direct edge, entered at the
-// emission time; a self pair over the loop.
-int64_t timeline_complete(Topology* top, const std::vector<int32_t>& sv,
-                          const std::vector<int32_t>& dv, const uint64_t* weight,
-                          const uint64_t* now, int64_t n, const WatchSet& ws,
-                          const TimelineOut& to, ShdTimelineStats* ts) {
-    const HostGraph& g = top->g;
-    const int64_t ne = (int64_t)ws.eids.size();
-    const std::vector<int32_t> pe = complete_pair_eids(top, sv, dv, n);
-    for (int64_t i = 0; i < n; i++) {
-        const int32_t s = sv[(size_t)i], d = dv[(size_t)i];
-        if (s < 0 || d < 0) continue;  // counted by the caller
-        const int32_t e = pe[(size_t)i];
-        if (e < 0) {
-            ts->broken++;
-            continue;
-        }
-        ts->routed++;
-        const uint64_t w = weight ? weight[i] : 1, t = now ? now[i] : 0;
-        const int64_t h0 = ts->hits;
-        const int32_t ke = ws.edge(e), kv = ws.vertex(d);
-        if (ke >= 0) to.add(s != g.eu[(size_t)e] ? ne + ke : ke, t, w, ts);
-        double lat = 0.0;
-        lat += g.elat[(size_t)e];
-        if (kv >= 0) to.add(ne + kv, t + lat_ns(lat), w, ts);
-        if (ts->hits > h0) ts->flows_hit++;
-    }
-    return ts->hits;
-}
-
-// SSSP topologies: the distinct sources in chunks -- chains from the batch kernel's pair records
-// or the replay (chunk_chains), whatever "load_walk" says -- link load's validation, then the mark
-// and time walks of topo_timeline.hip; the hops of the flows with a hit are staged per chunk and
-// die with it, the bins are the call's and copied out once the last chunk is walked
-int64_t timeline_replay(Topology* top, const std::vector<int32_t>& sv,
-                        const std::vector<int32_t>& dv, const uint64_t* weight,
-                        const uint64_t* now, int64_t n, const WatchSet& wset,
-                        const TimelineOut& to, ShdTimelineStats* ts) {
-    ReplayReqs R;
-    int r = group_replay_requests(top, sv, dv, n, &ts->ids_ms, false, R);
-    if (r) return r;
-    hipStream_t st = top->stream;
-    const size_t nv = R.nv, mmax = R.mmax;
-    const size_t rows = 2 * wset.eids.size() + wset.vids.size();
-    const size_t nacc = rows * ((size_t)to.nbins + 2);
-    ts->sources = R.nsrc;
-
-    DevWatch dw;
-    r = dw.upload(top, wset);
-    if (r) return r;
-    std::vector<unsigned long long> rw(nv, 1ull), rnow(nv, 0ull);
-    if (weight)
-        for (size_t q = 0; q < nv; q++) rw[q] = weight[R.order[q]];
-    if (now)
-        for (size_t q = 0; q < nv; q++) rnow[q] = now[R.order[q]];
-    DevBuf<int32_t> d_hops;
-    DevBuf<unsigned long long> d_w, d_now, d_acc, d_cnt, d_pcnt, d_tcnt;
-    DevBuf<int64_t> d_seg, d_coff;
-    DevBuf<uint2> d_stage;
-    HIPCHK(d_w.ensure(nv)); HIPCHK(d_now.ensure(nv));
-    HIPCHK(d_hops.ensure(nv));
-    HIPCHK(d_acc.ensure(nacc));
-    HIPCHK(d_cnt.ensure(LD_COUNT)); HIPCHK(d_pcnt.ensure(LD_COUNT)); HIPCHK(d_tcnt.ensure(TL_COUNT));
-    HIPCHK(d_seg.ensure(mmax + 1)); HIPCHK(d_coff.ensure(mmax + 1));
-    HIPCHK(hipMemcpy(d_w.p, rw.data(), 8 * nv, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_now.p, rnow.data(), 8 * nv, hipMemcpyHostToDevice));
-    HIPCHK(hipMemsetAsync(d_acc.p, 0, 8 * nacc, st));
-    HIPCHK(hipMemsetAsync(d_cnt.p, 0, 8 * LD_COUNT, st));
-    HIPCHK(hipMemsetAsync(d_tcnt.p, 0, 8 * TL_COUNT, st));
-    TimeBins tb;
-    tb.acc = d_acc.p;
-    tb.rows = (int64_t)rows;
-    tb.nbins = to.nbins;
-    tb.t0 = to.t0;
-    tb.binNs = to.binNs;
-
-    unsigned long long pcnt[LD_COUNT] = {};  // the pair walks' validation, as load_replay
-    for (int s0 = 0; s0 < R.nsrc; s0 += R.chunk) {
-        const int s1 = std::min(R.nsrc, s0 + R.chunk);
-        TraceReqs rq = R.reqs(s0, s1);
-        const size_t q0 = R.srcStart[(size_t)s0], m = (size_t)rq.n;
-        HIPCHK(hipMemsetAsync(d_seg.p, 0, 8 * (m + 1), st));
-        r = chunk_chains(top, R, s0, s1, &rq,
-                         [&](const TraceReqs& q, bool) {
-                             HIPCHK(hipMemsetAsync(d_pcnt.p, 0, 8 * LD_COUNT, st));
-                             HIPCHK(launch_load_validate_pairs(R.csr, R.pc, q, d_w.p + q0,
-                                                               d_hops.p + q0, d_pcnt.p,
-                                                               R.d_broken.p, st));
-                             return 0;
-                         },
-                         &ts->batch_ms, &ts->batch_sources, &ts->batch_fallback);
-        if (r) return r;
-        // both chain sources write the same segments and bins: each takes its requests
-        const bool pairs = R.mixed && R.nfall < s1 - s0;
-        unsigned long long c[LD_COUNT] = {};
-        if (pairs) {
-            HIPCHK(hipMemcpyAsync(c, d_pcnt.p, 8 * LD_COUNT, hipMemcpyDeviceToHost, st));
-            HIPCHK(launch_timeline_mark_pairs(R.csr, R.pc, R.ids, rq, d_hops.p + q0, dw.cw, d_seg.p,
-                                              d_tcnt.p, st));
-        }
-        if (R.nfall > 0) {
-            HIPCHK(launch_load_validate(R.csr, R.ws, rq, d_w.p + q0, d_hops.p + q0, d_cnt.p, st));
-            HIPCHK(launch_timeline_mark(R.csr, R.ws, R.ids, rq, d_hops.p + q0, dw.cw, d_seg.p,
-                                        d_tcnt.p, st));
-        }
-        HIPCHK(trace_exclusive_scan(d_seg.p, d_coff.p, (int64_t)m + 1, st));
-        int64_t tot = 0;
-        HIPCHK(hipMemcpy(&tot, d_coff.p + m, 8, hipMemcpyDeviceToHost));
-        HIPCHK(d_stage.ensure((size_t)std::max<int64_t>(1, tot)));
-        if (pairs && tot > 0)
-            HIPCHK(launch_timeline_time_pairs(R.csr, R.pc, R.ids, rq, d_w.p + q0, d_now.p + q0,
-                                              d_hops.p + q0, dw.cw, d_coff.p, d_stage.p, tb,
-                                              d_tcnt.p, st));
-        if (R.nfall > 0 && tot > 0)
-            HIPCHK(launch_timeline_time(R.csr, R.ws, R.ids, rq, d_w.p + q0, d_now.p + q0,
-                                        d_hops.p + q0, dw.cw, d_coff.p, d_stage.p, tb, d_tcnt.p, st));
-        HIPCHK(hipEventRecord(R.ev.e[2], st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int i = 0; i < LD_COUNT; i++) pcnt[i] += c[i];
-        r = chunk_times(R, &ts->replay_ms, &ts->kernel_ms);
-        if (r) return r;
-        ts->chunks++;
-    }
-
-    unsigned long long cnt[LD_COUNT] = {}, tcnt[TL_COUNT] = {};
-    std::vector<unsigned long long> acc(nacc);
-    HIPCHK(hipMemcpyAsync(cnt, d_cnt.p, 8 * LD_COUNT, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(tcnt, d_tcnt.p, 8 * TL_COUNT, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(acc.data(), d_acc.p, 8 * nacc, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const size_t nb = rows * (size_t)to.nbins;
-    if (nb) std::copy(acc.begin(), acc.begin() + nb, to.bins);
-    if (to.outside) std::copy(acc.begin() + nb, acc.end(), to.outside);
-    ts->routed = (int64_t)(cnt[LD_ROUTED] + pcnt[LD_ROUTED]);
-    ts->broken = (int64_t)(cnt[LD_BROKEN] + pcnt[LD_BROKEN]);
-    ts->flows_hit = (int64_t)tcnt[TL_FLOWS];
-    ts->in_range = (int64_t)tcnt[TL_IN];
-    ts->before = (int64_t)tcnt[TL_BEFORE];
-    ts->after = (int64_t)tcnt[TL_AFTER];
-    ts->staged_hops = (int64_t)tcnt[TL_STAGED];
-    ts->hits = ts->in_range + ts->before + ts->after;
-    return ts->hits;
-}
-
-// ---------------------------------------------------------------------------------------------
-// link monitor (include/shd_topology_abi.h shdtopo_monitor_*; kernels in topo_monitor.hip)
-// ---------------------------------------------------------------------------------------------
-static_assert(sizeof(MonRec) == 16, "MonRec is one 16-B load");
-
-// One monitor: the watch set and the bin geometry of a timeline call, kept; the hit index over
-// the column pairs of the geometry it was built for; cumulative bins and counters.  The device
-// parts appear with the first use of a device: a complete topology's host feeds walk h_off /
-// h_rec into h_acc and never touch one; its device feeds upload that index once.
-struct LinkMonitor {
-    WatchSet ws;
-    uint64_t t0 = 0, binNs = 0;
-    int64_t nbins = 0, rows = 0;
-    // the index
-    bool prepared = false, devIndex = false;
-    uint64_t idxSetGen = 0, idxGeomGen = 0;
-    std::vector<int32_t> idxAttached;
-    int64_t A = 0, nrec = 0;
-    DevBuf<int64_t> d_off;
-    DevBuf<MonRec> d_rec;
-    std::vector<int64_t> h_off;  // complete topologies
-    std::vector<MonRec> h_rec;
-    // bins rows x nbins, then the outside pairs rows x 2: device (every kernel feed) + host (the
-    // host walk of a complete topology); a read sums the two
-    DevBuf<unsigned long long> d_acc, d_cnt;
-    bool devBins = false;
-    std::vector<uint64_t> h_acc;
-    int64_t hcum[MN_COUNT] = {}, hlast[MN_COUNT] = {};
-    int64_t unattachedCum = 0;  // of the device counters' MN_BAD: the host feeds' share
-    bool lastOnDevice = false, lastHostForm = false;
-    // one event: recorded by every kernel feed on its stream; ek0 / ek1 bracket the last kernel
-    hipEvent_t ev = nullptr, ek0 = nullptr, ek1 = nullptr;
-    hipStream_t lastStream = nullptr;
-    bool pending = false, timed = false;
-    DevBuf<int32_t> b_src, b_dst;  // the host feeds' staging
-    DevBuf<unsigned long long> b_w, b_now;
-    DevBuf<uint8_t> b_dl;
-    ShdMonitorStats st{};
-    ~LinkMonitor() {
-        for (hipEvent_t e : {ev, ek0, ek1})
-            if (e) (void)hipEventDestroy(e);
-    }
-    size_t nacc() const { return (size_t)rows * ((size_t)nbins + 2); }
-};
-
-std::atomic<int> g_nextMonitor{0};
-
-LinkMonitor* monitor_of(Topology* top, int id) {
-    for (auto& m : top->monitors)
-        if (m.first == id) return m.second;
-    return nullptr;
-}
-
-// wait for the monitor's feeds and the library's stream
-int monitor_sync(Topology* top, LinkMonitor& m) {
-    if (!top->devInit) return 0;
-    HIPCHK(hipSetDevice(top->devId));
-    if (m.pending) HIPCHK(hipEventSynchronize(m.ev));
-    m.pending = false;
-    HIPCHK(hipStreamSynchronize(top->stream));
-    return 0;
-}
-
-void monitors_release(Topology* top) {
-    for (auto& m : top->monitors) {
-        (void)monitor_sync(top, *m.second);
-        delete m.second;
-    }
-    top->monitors.clear();
-}
-
-void monitor_drop_index(LinkMonitor& m) {
-    m.prepared = m.devIndex = false;
-    m.d_off.release();
-    m.d_rec.release();
-    std::vector<int64_t>().swap(m.h_off);
-    std::vector<MonRec>().swap(m.h_rec);
-    m.A = m.nrec = 0;
-    m.st.index_pairs = m.st.index_records = m.st.index_bytes = 0;
-}
-
-// the device side of a monitor: events, bins, counters (zeroed once)
-int monitor_dev(Topology* top, LinkMonitor& m) {
-    int r = dev_init(top);
-    if (r) return r;
-    if (m.devBins) return 0;
-    if (!m.ev) HIPCHK(hipEventCreate(&m.ev));
-    if (!m.ek0) HIPCHK(hipEventCreate(&m.ek0));
-    if (!m.ek1) HIPCHK(hipEventCreate(&m.ek1));
-    HIPCHK(m.d_acc.ensure(std::max<size_t>(1, m.nacc())));
-    HIPCHK(m.d_cnt.ensure(2 * MN_COUNT));
-    HIPCHK(hipMemsetAsync(m.d_acc.p, 0, 8 * std::max<size_t>(1, m.nacc()), top->stream));
-    HIPCHK(hipMemsetAsync(m.d_cnt.p, 0, 8 * 2 * MN_COUNT, top->stream));
-    HIPCHK(hipStreamSynchronize(top->stream));
-    m.devBins = true;
-    return 0;
-}
-
-// the bytes an index may take (option "monitor_index_mb")
-int monitor_cap_bytes(Topology* top, bool device, double* cap) {
-    *cap = 1e30;
-    if (top->monitorIndexMb > 0) {
-        *cap = top->monitorIndexMb * 1048576.0;
-    } else if (device) {
-        size_t fr = 0, tot = 0;
-        HIPCHK(hipMemGetInfo(&fr, &tot));
-        *cap = (double)fr / 2;
-    }
-    return 0;
-}
-
-// Complete topologies, on the host as timeline_complete: every pair is one hop over the direct
-// edge, entered at offset 0, arrival at ns(0.0 + latency); a self pair over the loop.  The rows
-// of sources are taken a block at a time (complete_pair_eids keeps a map of its requests).
-int64_t monitor_index_complete(Topology* top, LinkMonitor& m) {
-    const HostGraph& g = top->g;
-    const int64_t A = top->A, ne = (int64_t)m.ws.eids.size();
-    double cap = 0;
-    int r = monitor_cap_bytes(top, false, &cap);
-    if (r) return r;
-    const double offBytes = 8.0 * ((double)A * A + 1);
-    if (offBytes > cap) return -5;
-    m.h_off.assign((size_t)(A * A + 1), 0);
-    const int64_t blk =
-        std::max<int64_t>(1, std::min<int64_t>(A, (1 << 22) / std::max<int64_t>(1, A)));
-    for (int64_t c0 = 0; c0 < A; c0 += blk) {
-        const int64_t c1 = std::min(A, c0 + blk), n = (c1 - c0) * A;
-        std::vector<int32_t> sv((size_t)n), dv((size_t)n);
-        for (int64_t i = 0; i < n; i++) {
-            sv[(size_t)i] = top->attached[(size_t)(c0 + i / A)];
-            dv[(size_t)i] = top->attached[(size_t)(i % A)];
-        }
-        const std::vector<int32_t> pe = complete_pair_eids(top, sv, dv, n);
-        for (int64_t i = 0; i < n; i++) {
-            m.h_off[(size_t)(c0 * A + i)] = (int64_t)m.h_rec.size();
-            const int32_t e = pe[(size_t)i];
-            if (e < 0) {
-                m.st.broken_pairs++;
-                continue;
-            }
-            const int32_t ke = m.ws.edge(e), kv = m.ws.vertex(dv[(size_t)i]);
-            if (ke >= 0)
-                m.h_rec.push_back(
-                    MonRec{0, (uint32_t)(sv[(size_t)i] != g.eu[(size_t)e] ? ne + ke : ke), 0u});
-            double lat = 0.0;
-            lat += g.elat[(size_t)e];
-            if (kv >= 0) m.h_rec.push_back(MonRec{lat_ns(lat), (uint32_t)(ne + kv), 0u});
-        }
-        if (offBytes + 16.0 * (double)m.h_rec.size() > cap) return -5;
-        m.st.chunks++;
-    }
-    m.h_off[(size_t)(A * A)] = (int64_t)m.h_rec.size();
-    m.st.sources = A;
-    return (int64_t)m.h_rec.size();
-}
-
-// SSSP topologies: the source columns in blocks of one chunk, each block's requests (source,
-// every column) -- chains as a timeline call's (chunk_chains), link load's validation, the
-// crossings' count walk (records per pair, in request = pair order), the timeline's mark walk (the
-// staging segments), the scans, then the fill pass of topo_monitor.hip into the block's records.
-// A block's records are allocated once its count says the index still fits; the blocks are put
-// together when the last one is filled.
-int64_t monitor_index_replay(Topology* top, LinkMonitor& m) {
-    int r = dev_init(top);
-    if (r) return r;
-    const int64_t A = top->A;
-    const size_t nw = m.ws.eids.size() + m.ws.vids.size();
-    double cap = 0;
-    r = monitor_cap_bytes(top, true, &cap);
-    if (r) return r;
-    const double offBytes = 8.0 * ((double)A * A + 1);
-    if (offBytes > cap) return -5;
-    hipStream_t st = nullptr;
-    HIPCHK(m.d_off.ensure((size_t)(A * A + 1)));
-
-    DevWatch dw;
-    DevBuf<int32_t> d_hops;
-    DevBuf<unsigned long long> d_w, d_wcount, d_wweight, d_cnt, d_pcnt, d_ccnt, d_tcnt;
-    DevBuf<int64_t> d_lcnt, d_gcnt, d_goff, d_seg, d_coff;
-    DevBuf<uint2> d_stage;
-    std::vector<std::unique_ptr<DevBuf<MonRec>>> blocks;
-    std::vector<int64_t> blockRecs;
-    int64_t total = 0;
-    unsigned long long broken = 0;
-    // the first block's size is a guess: a block that turns out wider than a chunk is taken again
-    int64_t B = top->traceChunk > 0 ? top->traceChunk : 256;
-    for (int64_t c0 = 0; c0 < A;) {
-        B = std::max<int64_t>(1, std::min<int64_t>(B, (int64_t)(1 << 25) / A));
-        const int64_t c1 = std::min(A, c0 + B), n = (c1 - c0) * A;
-        std::vector<int32_t> sv((size_t)n), dv((size_t)n);
-        for (int64_t i = 0; i < n; i++) {
-            sv[(size_t)i] = top->attached[(size_t)(c0 + i / A)];
-            dv[(size_t)i] = top->attached[(size_t)(i % A)];
-        }
-        ReplayReqs R;
-        double ids_ms = 0;
-        r = group_replay_requests(top, sv, dv, n, &ids_ms, false, R);
-        if (r) return r;
-        if (R.nsrc > R.chunk) {
-            B = R.chunk;
-            continue;
-        }
-        if (!st) {
-            st = top->stream;
-            r = dw.upload(top, m.ws);
-            if (r) return r;
-            HIPCHK(d_wcount.ensure(nw)); HIPCHK(d_wweight.ensure(nw));
-            HIPCHK(d_cnt.ensure(LD_COUNT)); HIPCHK(d_pcnt.ensure(LD_COUNT));
-            HIPCHK(d_ccnt.ensure(CR_COUNT)); HIPCHK(d_tcnt.ensure(TL_COUNT));
-            HIPCHK(hipMemsetAsync(d_wcount.p, 0, 8 * nw, st));
-            HIPCHK(hipMemsetAsync(d_wweight.p, 0, 8 * nw, st));
-            HIPCHK(hipMemsetAsync(d_cnt.p, 0, 8 * LD_COUNT, st));
-            HIPCHK(hipMemsetAsync(d_ccnt.p, 0, 8 * CR_COUNT, st));
-            HIPCHK(hipMemsetAsync(d_tcnt.p, 0, 8 * TL_COUNT, st));
-        }
-        CrossWatch cw = dw.cw;
-        cw.wcount = d_wcount.p;
-        cw.wweight = d_wweight.p;
-        const size_t nq = (size_t)n;
-        if (R.nv != nq) return -3;  // (every request has both ends attached)
-        if (d_w.n < nq) {
-            const std::vector<unsigned long long> ones(nq, 1ull);
-            HIPCHK(d_w.ensure(nq));
-            HIPCHK(hipMemcpy(d_w.p, ones.data(), 8 * nq, hipMemcpyHostToDevice));
-        }
-        HIPCHK(d_hops.ensure(nq));
-        HIPCHK(d_lcnt.ensure(nq + 1)); HIPCHK(d_gcnt.ensure(nq + 1)); HIPCHK(d_goff.ensure(nq + 1));
-        HIPCHK(d_seg.ensure(nq + 1)); HIPCHK(d_coff.ensure(nq + 1));
-        HIPCHK(hipMemsetAsync(d_lcnt.p, 0, 8 * (nq + 1), st));
-        HIPCHK(hipMemsetAsync(d_gcnt.p, 0, 8 * (nq + 1), st));
-        HIPCHK(hipMemsetAsync(d_seg.p, 0, 8 * (nq + 1), st));
-        TraceReqs rq = R.reqs(0, R.nsrc);
-        r = chunk_chains(top, R, 0, R.nsrc, &rq,
-                         [&](const TraceReqs& q, bool) {
-                             HIPCHK(hipMemsetAsync(d_pcnt.p, 0, 8 * LD_COUNT, st));
-                             HIPCHK(launch_load_validate_pairs(R.csr, R.pc, q, d_w.p, d_hops.p,
-                                                               d_pcnt.p, R.d_broken.p, st));
-                             return 0;
-                         },
-                         &m.st.batch_ms, &m.st.batch_sources, &m.st.batch_fallback);
-        if (r) return r;
-        // both chain sources write the same counts, segments and records: each takes its requests
-        const bool pairs = R.mixed && R.nfall < R.nsrc;
-        unsigned long long c[LD_COUNT] = {};
-        if (pairs) {
-            HIPCHK(hipMemcpyAsync(c, d_pcnt.p, 8 * LD_COUNT, hipMemcpyDeviceToHost, st));
-            HIPCHK(launch_cross_count_pairs(R.csr, R.pc, R.ids, rq, d_w.p, d_hops.p, cw, d_lcnt.p,
-                                            d_gcnt.p, d_ccnt.p, st));
-            HIPCHK(launch_timeline_mark_pairs(R.csr, R.pc, R.ids, rq, d_hops.p, dw.cw, d_seg.p,
-                                              d_tcnt.p, st));
-        }
-        if (R.nfall > 0) {
-            HIPCHK(launch_load_validate(R.csr, R.ws, rq, d_w.p, d_hops.p, d_cnt.p, st));
-            HIPCHK(launch_cross_count(R.csr, R.ws, R.ids, rq, d_w.p, d_hops.p, cw, d_lcnt.p,
-                                      d_gcnt.p, d_ccnt.p, st));
-            HIPCHK(launch_timeline_mark(R.csr, R.ws, R.ids, rq, d_hops.p, dw.cw, d_seg.p,
-                                        d_tcnt.p, st));
-        }
-        HIPCHK(trace_exclusive_scan(d_gcnt.p, d_goff.p, n + 1, st));
-        HIPCHK(trace_exclusive_scan(d_seg.p, d_coff.p, n + 1, st));
-        int64_t tot = 0, nstage = 0;
-        HIPCHK(hipMemcpyAsync(&tot, d_goff.p + n, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(&nstage, d_coff.p + n, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        broken += c[LD_BROKEN];
-        if (offBytes + 16.0 * (double)(total + tot) > cap) return -5;
-        blocks.emplace_back(new DevBuf<MonRec>());
-        DevBuf<MonRec>& rec = *blocks.back();
-        HIPCHK(rec.ensure((size_t)std::max<int64_t>(1, tot)));
-        HIPCHK(d_stage.ensure((size_t)std::max<int64_t>(1, nstage)));
-        if (pairs && tot > 0)
-            HIPCHK(launch_monitor_fill_pairs(R.csr, R.pc, R.ids, rq, d_hops.p, dw.cw, d_coff.p,
-                                             d_stage.p, d_goff.p, rec.p, st));
-        if (R.nfall > 0 && tot > 0)
-            HIPCHK(launch_monitor_fill(R.csr, R.ws, R.ids, rq, d_hops.p, dw.cw, d_coff.p,
-                                       d_stage.p, d_goff.p, rec.p, st));
-        HIPCHK(launch_monitor_offsets(d_goff.p, m.d_off.p + c0 * A, n + 1, total, st));
-        HIPCHK(hipEventRecord(R.ev.e[2], st));
-        HIPCHK(hipStreamSynchronize(st));
-        r = chunk_times(R, &m.st.replay_ms, &m.st.kernel_ms);
-        if (r) return r;
-        blockRecs.push_back(tot);
-        total += tot;
-        m.st.sources += R.nsrc;
-        m.st.chunks++;
-        B = R.chunk;
-        c0 = c1;
-    }
-    if (A == 0) {
-        const int64_t zero = 0;
-        HIPCHK(hipMemcpy(m.d_off.p, &zero, 8, hipMemcpyHostToDevice));
-    }
-    HIPCHK(m.d_rec.ensure((size_t)std::max<int64_t>(1, total)));
-    int64_t at = 0;
-    for (size_t b = 0; b < blocks.size(); b++) {
-        if (blockRecs[b] > 0)
-            HIPCHK(hipMemcpyAsync(m.d_rec.p + at, blocks[b]->p,
-                                  sizeof(MonRec) * (size_t)blockRecs[b], hipMemcpyDeviceToDevice,
-                                  top->stream));
-        at += blockRecs[b];
-    }
-    HIPCHK(hipStreamSynchronize(top->stream));
-    if (st) {
-        unsigned long long cnt[LD_COUNT] = {};
-        HIPCHK(hipMemcpy(cnt, d_cnt.p, 8 * LD_COUNT, hipMemcpyDeviceToHost));
-        broken += cnt[LD_BROKEN];
-    }
-    m.st.broken_pairs = (int64_t)broken;
-    m.devIndex = true;
-    return total;
-}
-
-// whether the index is the current geometry's; sg: compute_geometry's result
-bool monitor_index_current(Topology* top, LinkMonitor& m, uint64_t sg) {
-    if (!m.prepared) return false;
-    if (m.idxSetGen == sg && m.idxGeomGen == top->geomGen) return true;
-    if (m.idxAttached != top->attached) return false;
-    m.idxSetGen = sg;  // (the set moved and came back: the same columns)
-    m.idxGeomGen = top->geomGen;
-    return true;
-}
-
-int64_t monitor_prepare_locked(Topology* top, LinkMonitor& m) {
-    const auto tstart = std::chrono::steady_clock::now();
-    int r = monitor_sync(top, m);
-    if (r) return r;
-    const uint64_t sg = compute_geometry(top);
-    monitor_drop_index(m);
-    if (m.rows == 0) return 0;  // no watches: no index
-    m.st.prepare_ms = m.st.replay_ms = m.st.kernel_ms = m.st.batch_ms = 0;
-    m.st.sources = m.st.chunks = m.st.batch_sources = m.st.batch_fallback = m.st.broken_pairs = 0;
-    const int64_t rec =
-        top->isComplete ? monitor_index_complete(top, m) : monitor_index_replay(top, m);
-    if (rec < 0) {
-        monitor_drop_index(m);
-        return rec;
-    }
-    m.prepared = true;
-    m.A = top->A;
-    m.nrec = rec;
-    m.idxSetGen = sg;
-    m.idxGeomGen = top->geomGen;
-    m.idxAttached = top->attached;
-    m.st.index_pairs = m.A * m.A;
-    m.st.index_records = rec;
-    m.st.index_bytes = 8 * (m.A * m.A + 1) + 16 * rec;
-    m.st.prepares++;
-    m.st.prepare_ms = std::chrono::duration<double, std::milli>(
-        std::chrono::steady_clock::now() - tstart).count();
-    return rec;
-}
-
-// prepared for the current geometry, or prepare: 0, or the prepare's error
-int64_t monitor_ready(Topology* top, LinkMonitor& m) {
-    const uint64_t sg = compute_geometry(top);
-    if (monitor_index_current(top, m, sg)) return 0;
-    const int64_t r = monitor_prepare_locked(top, m);
-    return r < 0 ? r : 0;
-}
-
-// the index on the device for a kernel feed (a complete topology's is uploaded once)
-int monitor_dev_index(Topology* top, LinkMonitor& m) {
-    if (m.devIndex) return 0;
-    HIPCHK(m.d_off.ensure(m.h_off.size()));
-    HIPCHK(m.d_rec.ensure(std::max<size_t>(1, m.h_rec.size())));
-    HIPCHK(hipMemcpy(m.d_off.p, m.h_off.data(), 8 * m.h_off.size(), hipMemcpyHostToDevice));
-    if (!m.h_rec.empty())
-        HIPCHK(hipMemcpy(m.d_rec.p, m.h_rec.data(), sizeof(MonRec) * m.h_rec.size(),
-                         hipMemcpyHostToDevice));
-    m.devIndex = true;
-    return 0;
-}
-
-// One kernel feed on st: the monitor's stream protocol, the last feed's counters zeroed, the
-// kernel between ek0 / ek1, the event recorded.  w32 or w64 carries the weights (or neither).
-int monitor_launch(Topology* top, LinkMonitor& m, const int32_t* d_src, const int32_t* d_dst,
-                   const uint32_t* w32, const unsigned long long* w64,
-                   const unsigned long long* d_now, const uint8_t* d_dl, int64_t n, hipStream_t st) {
-    if (m.pending && st != m.lastStream) HIPCHK(hipStreamWaitEvent(st, m.ev, 0));
-    MonIndex ix;
-    ix.off = m.d_off.p;
-    ix.rec = m.d_rec.p;
-    ix.nrec = m.nrec;
-    ix.A = (int32_t)m.A;
-    TimeBins tb;
-    tb.acc = m.d_acc.p;
-    tb.rows = m.rows;
-    tb.nbins = m.nbins;
-    tb.t0 = m.t0;
-    tb.binNs = m.binNs;
-    HIPCHK(hipMemsetAsync(m.d_cnt.p + MN_COUNT, 0, 8 * MN_COUNT, st));
-    HIPCHK(hipEventRecord(m.ek0, st));
-    if (w64)
-        HIPCHK(launch_monitor_feed_u64(n, d_src, d_dst, w64, d_now, d_dl, ix, tb, m.d_cnt.p, st));
-    else
-        HIPCHK(launch_monitor_feed(n, d_src, d_dst, w32, d_now, d_dl, ix, tb, m.d_cnt.p, st));
-    HIPCHK(hipEventRecord(m.ek1, st));
-    HIPCHK(hipEventRecord(m.ev, st));
-    m.lastStream = st;
-    m.pending = m.timed = true;
-    m.lastOnDevice = true;
-    return 0;
-}
-
-// A host feed by columns (-1: an end that is no column).  Complete topologies walk the host index;
-// the others stage the arrays, run the feed kernel and wait for it.
-int64_t monitor_feed_cols(Topology* top, LinkMonitor& m, const std::vector<int32_t>& sc,
-                          const std::vector<int32_t>& dc, const uint64_t* weight,
-                          const uint64_t* now, const uint8_t* delivered, int64_t n) {
-    m.st.feeds++;
-    if (m.rows == 0 || n == 0) return 0;
-    const int64_t rr = monitor_ready(top, m);
-    if (rr < 0) return rr;
-    m.lastHostForm = true;
-    if (top->isComplete) {
-        if (m.h_acc.empty()) m.h_acc.assign(m.nacc(), 0);
-        int64_t* c = m.hlast;
-        std::fill(c, c + MN_COUNT, (int64_t)0);
-        const int64_t A = m.A;
-        for (int64_t i = 0; i < n; i++) {
-            if (delivered && !delivered[i]) {
-                c[MN_SKIPPED]++;
-                continue;
-            }
-            if (sc[(size_t)i] < 0 || dc[(size_t)i] < 0) {
-                c[MN_BAD]++;
-                continue;
-            }
-            c[MN_FED]++;
-            const size_t p = (size_t)((int64_t)sc[(size_t)i] * A + dc[(size_t)i]);
-            const uint64_t w = weight ? weight[i] : 1, t = now ? now[i] : 0;
-            if (m.h_off[p + 1] > m.h_off[p]) c[MN_FLOWS]++;
-            for (int64_t k = m.h_off[p]; k < m.h_off[p + 1]; k++) {
-                // TimelineOut::add on the cumulative bins
-                const MonRec& rec = m.h_rec[(size_t)k];
-                const uint64_t tt = t + rec.offNs;
-                uint64_t* outside = m.h_acc.data() + (size_t)(m.rows * m.nbins) + 2 * rec.row;
-                if (tt < m.t0) {
-                    outside[0] += w;
-                    c[MN_BEFORE]++;
-                } else if (m.nbins > 0 && (tt - m.t0) / m.binNs < (uint64_t)m.nbins) {
-                    m.h_acc[(size_t)(rec.row * m.nbins + (int64_t)((tt - m.t0) / m.binNs))] += w;
-                    c[MN_IN]++;
-                } else {
-                    outside[1] += w;
-                    c[MN_AFTER]++;
-                }
-            }
-        }
-        for (int i = 0; i < MN_COUNT; i++) m.hcum[i] += c[i];
-        m.lastOnDevice = false;
-        m.timed = false;
-        return c[MN_IN] + c[MN_BEFORE] + c[MN_AFTER];
-    }
-    int r = monitor_dev(top, m);
-    if (r) return r;
-    hipStream_t st = top->stream;
-    const size_t nn = (size_t)n;
-    HIPCHK(m.b_src.ensure(nn)); HIPCHK(m.b_dst.ensure(nn));
-    HIPCHK(hipMemcpyAsync(m.b_src.p, sc.data(), 4 * nn, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(m.b_dst.p, dc.data(), 4 * nn, hipMemcpyHostToDevice, st));
-    if (weight) {
-        HIPCHK(m.b_w.ensure(nn));
-        HIPCHK(hipMemcpyAsync(m.b_w.p, weight, 8 * nn, hipMemcpyHostToDevice, st));
-    }
-    if (now) {
-        HIPCHK(m.b_now.ensure(nn));
-        HIPCHK(hipMemcpyAsync(m.b_now.p, now, 8 * nn, hipMemcpyHostToDevice, st));
-    }
-    if (delivered) {
-        HIPCHK(m.b_dl.ensure(nn));
-        HIPCHK(hipMemcpyAsync(m.b_dl.p, delivered, nn, hipMemcpyHostToDevice, st));
-    }
-    r = monitor_launch(top, m, m.b_src.p, m.b_dst.p, nullptr, weight ? m.b_w.p : nullptr,
-                       now ? m.b_now.p : nullptr, delivered ? m.b_dl.p : nullptr, n, st);
-    if (r) return r;
-    unsigned long long c[MN_COUNT] = {};
-    HIPCHK(hipMemcpyAsync(c, m.d_cnt.p + MN_COUNT, 8 * MN_COUNT, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    m.pending = false;
-    m.unattachedCum += (int64_t)c[MN_BAD];
-    return (int64_t)(c[MN_IN] + c[MN_BEFORE] + c[MN_AFTER]);
-}
-
-}  // namespace
-
-extern "C" {
-
-int64_t shdtopo_trace_routes(Topology* top, const uint32_t* srcIP, const uint32_t* dstIP, int64_t n,
-                             ShdRoute* routes, int32_t* vertices, int32_t* edges, int64_t cap) {
-    if (!top || n < 0 || cap < 0 || n > 0x7FFFFFFE) return -1;
-    if (n > 0 && (!srcIP || !dstIP || !routes)) return -1;
-    if (cap > 0 && (!vertices || !edges)) return -1;
-    const auto t0 = std::chrono::steady_clock::now();
-    std::lock_guard<std::mutex> lk(top->buildMu);
-    ShdTraceStats ts{};
-    ts.requests = n;
-    compute_geometry(top);
-    // both ends on a vertex of the current attached set (a table column), else status 1
-    std::vector<int32_t> sv((size_t)n), dv((size_t)n);
-    int64_t nvalid = 0;
-    for (int64_t i = 0; i < n; i++) {
-        int32_t s = vertex_of_ip(top, srcIP[i]), d = vertex_of_ip(top, dstIP[i]);
-        if (s >= 0 && (s >= top->g.V || top->colOf[(size_t)s] < 0)) s = -1;
-        if (d >= 0 && (d >= top->g.V || top->colOf[(size_t)d] < 0)) d = -1;
-        sv[(size_t)i] = s;
-        dv[(size_t)i] = d;
-        if (s >= 0 && d >= 0) nvalid++;
-    }
-    int64_t total = 0;
-    if (top->isComplete) {
-        total = trace_complete(top, sv, dv, n, routes, vertices, edges, cap);
-    } else if (nvalid == 0) {
-        for (int64_t i = 0; i < n; i++) routes[i] = route_blank(kTraceUnattached);
-    } else {
-        total = trace_replay(top, sv, dv, n, routes, vertices, edges, cap, &ts);
-    }
-    ts.entries = total;
-    ts.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    top->traceStats = ts;
-    return total;
-}
-
-int shdtopo_trace_stats(Topology* top, ShdTraceStats* out) {
-    if (!top || !out) return -1;
-    std::lock_guard<std::mutex> lk(top->buildMu);
-    *out = top->traceStats;
-    return 0;
-}
-
-int64_t shdtopo_link_load(Topology* top, const uint32_t* srcIP, const uint32_t* dstIP,
-                          const uint64_t* weight, int64_t n, uint64_t* edgeLoad,
-                          uint64_t* vertexLoad) {
-    if (!top || n < 0 || n > 0x7FFFFFFE) return -1;
-    if (n > 0 && (!srcIP || !dstIP)) return -1;
-    const auto t0 = std::chrono::steady_clock::now();
-    std::lock_guard<std::mutex> lk(top->buildMu);
-    ShdLoadStats ls{};
-    ls.requests = n;
-    compute_geometry(top);
-    // the outputs are overwritten, not accumulated into
-    if (edgeLoad) std::fill(edgeLoad, edgeLoad + 2 * (size_t)top->g.E, (uint64_t)0);
-    if (vertexLoad) std::fill(vertexLoad, vertexLoad + (size_t)top->g.V, (uint64_t)0);
-    // both ends on a vertex of the current attached set, as a trace
-    std::vector<int32_t> sv((size_t)n), dv((size_t)n);
-    int64_t nvalid = 0;
-    for (int64_t i = 0; i < n; i++) {
-        int32_t s = vertex_of_ip(top, srcIP[i]), d = vertex_of_ip(top, dstIP[i]);
-        if (s >= 0 && (s >= top->g.V || top->colOf[(size_t)s] < 0)) s = -1;
-        if (d >= 0 && (d >= top->g.V || top->colOf[(size_t)d] < 0)) d = -1;
-        sv[(size_t)i] = s;
-        dv[(size_t)i] = d;
-        if (s >= 0 && d >= 0) nvalid++;
-    }
-    ls.unattached = n - nvalid;
-    int64_t routed = 0;
-    if (top->isComplete) routed = load_complete(top, sv, dv, weight, n, edgeLoad, vertexLoad, &ls);
-    else if (nvalid > 0) routed = load_replay(top, sv, dv, weight, n, edgeLoad, vertexLoad, &ls);
-    ls.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    top->loadStats = ls;
-    return routed;
-}
-
-int shdtopo_link_load_stats(Topology* top, ShdLoadStats* out) {
-    if (!top || !out) return -1;
-    std::lock_guard<std::mutex> lk(top->buildMu);
-    *out = top->loadStats;
-    return 0;
-}
-
-int64_t shdtopo_link_crossings(Topology* top, const uint32_t* srcIP, const uint32_t* dstIP,
-                               const uint64_t* weight, int64_t n, const int32_t* watchEdge,
-                               int64_t ne, const int32_t* watchVertex, int64_t nv,
-                               int64_t* flowOffset, ShdCrossing* out, int64_t cap,
-                               uint64_t* watchCount, uint64_t* watchWeight) {
-    if (!top || n < 0 || n > 0x7FFFFFFE || ne < 0 || nv < 0 || cap < 0) return -1;
-    if (n > 0 && (!srcIP || !dstIP)) return -1;
-    if ((ne > 0 && !watchEdge) || (nv > 0 && !watchVertex) || (cap > 0 && !out)) return -1;
-    if (ne > top->g.E || nv > top->g.V) return -1;  // (more ids than there are: a duplicate)
-    const auto t0 = std::chrono::steady_clock::now();
-    std::lock_guard<std::mutex> lk(top->buildMu);
-    WatchSet ws;
-    if (!ws.init(top->g, watchEdge, ne, watchVertex, nv)) return -1;
-    ShdCrossStats cs{};
-    cs.requests = n;
-    compute_geometry(top);
-    // the outputs are overwritten, not accumulated into
-    if (flowOffset) std::fill(flowOffset, flowOffset + (size_t)n + 1, (int64_t)0);
-    if (watchCount) std::fill(watchCount, watchCount + (size_t)(ne + nv), (uint64_t)0);
-    if (watchWeight) std::fill(watchWeight, watchWeight + (size_t)(ne + nv), (uint64_t)0);
-    // both ends on a vertex of the current attached set, as a trace
-    std::vector<int32_t> sv((size_t)n), dv((size_t)n);
-    int64_t nvalid = 0;
-    for (int64_t i = 0; i < n; i++) {
-        int32_t s = vertex_of_ip(top, srcIP[i]), d = vertex_of_ip(top, dstIP[i]);
-        if (s >= 0 && (s >= top->g.V || top->colOf[(size_t)s] < 0)) s = -1;
-        if (d >= 0 && (d >= top->g.V || top->colOf[(size_t)d] < 0)) d = -1;
-        sv[(size_t)i] = s;
-        dv[(size_t)i] = d;
-        if (s >= 0 && d >= 0) nvalid++;
-    }
-    cs.unattached = n - nvalid;
-    int64_t total = 0;
-    if (top->isComplete)
-        total = cross_complete(top, sv, dv, weight, n, ws, flowOffset, out, cap, watchCount,
-                               watchWeight, &cs);
-    else if (nvalid > 0 && ne + nv > 0)  // an empty watch set: nothing to walk for
-        total = cross_replay(top, sv, dv, weight, n, ws, flowOffset, out, cap, watchCount,
-                             watchWeight, &cs);
-    cs.crossings = total < 0 ? 0 : total;
-    cs.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    top->crossStats = cs;
-    return total;
-}
-
-int shdtopo_link_crossings_stats(Topology* top, ShdCrossStats* out) {
-    if (!top || !out) return -1;
-    std::lock_guard<std::mutex> lk(top->buildMu);
-    *out = top->crossStats;
-    return 0;
-}
-
-int64_t shdtopo_link_timeline(Topology* top, const uint32_t* srcIP, const uint32_t* dstIP,
-                              const uint64_t* weight, const uint64_t* now, int64_t n,
-                              const int32_t* watchEdge, int64_t ne, const int32_t* watchVertex,
-                              int64_t nv, uint64_t t0, uint64_t binNs, int64_t nbins,
-                              uint64_t* bins, uint64_t* outside) {
-    if (!top || n < 0 || n > 0x7FFFFFFE || ne < 0 || nv < 0 || nbins < 0) return -1;
-    if (nbins > 0 && binNs == 0) return -1;
-    if (n > 0 && (!srcIP || !dstIP)) return -1;
-    if ((ne > 0 && !watchEdge) || (nv > 0 && !watchVertex)) return -1;
-    if (ne > top->g.E || nv > top->g.V) return -1;  // (more ids than there are: a duplicate)
-    const int64_t rows = 2 * ne + nv;
-    if (nbins > 0 && rows > (int64_t)0x7FFFFFFF / nbins) return -1;  // (a device buffer of rows x bins)
-    if (rows * nbins > 0 && !bins) return -1;
-    const auto tstart = std::chrono::steady_clock::now();
-    std::lock_guard<std::mutex> lk(top->buildMu);
-    WatchSet ws;
-    if (!ws.init(top->g, watchEdge, ne, watchVertex, nv)) return -1;
-    ShdTimelineStats ts{};
-    ts.requests = n;
-    compute_geometry(top);
-    // the outputs are overwritten, not accumulated into
-    if (bins) std::fill(bins, bins + (size_t)(rows * nbins), (uint64_t)0);
-    if (outside) std::fill(outside, outside + (size_t)(2 * rows), (uint64_t)0);
-    // both ends on a vertex of the current attached set, as a trace
-    std::vector<int32_t> sv((size_t)n), dv((size_t)n);
-    int64_t nvalid = 0;
-    for (int64_t i = 0; i < n; i++) {
-        int32_t s = vertex_of_ip(top, srcIP[i]), d = vertex_of_ip(top, dstIP[i]);
-        if (s >= 0 && (s >= top->g.V || top->colOf[(size_t)s] < 0)) s = -1;
-        if (d >= 0 && (d >= top->g.V || top->colOf[(size_t)d] < 0)) d = -1;
-        sv[(size_t)i] = s;
-        dv[(size_t)i] = d;
-        if (s >= 0 && d >= 0) nvalid++;
-    }
-    ts.unattached = n - nvalid;
-    const TimelineOut to{t0, binNs, nbins, bins, outside};
-    int64_t hits = 0;
-    if (rows == 0) hits = 0;  // an empty watch set: nothing to walk for
-    else if (top->isComplete) hits = timeline_complete(top, sv, dv, weight, now, n, ws, to, &ts);
-    else if (nvalid > 0) hits = timeline_replay(top, sv, dv, weight, now, n, ws, to, &ts);
-    if (hits < 0) ts.hits = 0;
-    ts.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tstart).count();
-    top->timelineStats = ts;
-    return hits;
-}
-
-int shdtopo_link_timeline_stats(Topology* top, ShdTimelineStats* out) {
-    if (!top || !out) return -1;
-    std::lock_guard<std::mutex> lk(top->buildMu);
-    *out = top->timelineStats;
-    return 0;
-}
-
-int shdtopo_monitor_new(Topology* top, const int32_t* watchEdge, int64_t ne,
-                        const int32_t* watchVertex, int64_t nv, uint64_t t0, uint64_t binNs,
-                        int64_t nbins) {
-    if (!top || ne < 0 || nv < 0 || nbins < 0) return -1;
-    if (nbins > 0 && binNs == 0) return -1;
-    if ((ne > 0 && !watchEdge) || (nv > 0 && !watchVertex)) return -1;
-    if (ne > top->g.E || nv > top->g.V) return -1;  // (more ids than there are: a duplicate)
-    const int64_t rows = 2 * ne + nv;
-    if (nbins > 0 && rows > (int64_t)0x7FFFFFFF / nbins) return -1;  // (a device buffer of rows x bins)
-    std::lock_guard<std::mutex> lk(top->buildMu);
-    std::unique_ptr<LinkMonitor> m(new LinkMonitor());
-    if (!m->ws.init(top->g, watchEdge, ne, watchVertex, nv)) return -1;
-    m->t0 = t0;
-    m->binNs = binNs;
-    m->nbins = nbins;
-    m->rows = rows;
-    const int id = g_nextMonitor.fetch_add(1);
-    top->monitors.emplace_back(id, m.release());
-    return id;
-}
-
-int shdtopo_monitor_free(Topology* top, int id) {
-    if (!top) return -1;
-    std::lock_guard<std::mutex> lk(top->buildMu);
-    for (size_t k = 0; k < top->monitors.size(); k++)
-        if (top->monitors[k].first == id) {
-            (void)monitor_sync(top, *top->monitors[k].second);
-            delete top->monitors[k].second;
-            top->monitors.erase(top->monitors.begin() + (std::ptrdiff_t)k);
-            return 0;
-        }
-    return -1;
-}
-
-int64_t shdtopo_monitor_prepare(Topology* top, int id) {
-    if (!top) return -1;
-    std::lock_guard<std::mutex> lk(top->buildMu);
-    LinkMonitor* m = monitor_of(top, id);
-    if (!m) return -1;
-    return monitor_prepare_locked(top, *m);
-}
-
-int64_t shdtopo_monitor_feed(Topology* top, int id, const uint32_t* srcIP, const uint32_t* dstIP,
-                             const uint64_t* weight, const uint64_t* now, const uint8_t* delivered,
-                             int64_t n) {
-    if (!top || n < 0 || n > 0x7FFFFFFE) return -1;
-    if (n > 0 && (!srcIP || !dstIP)) return -1;
-    std::lock_guard<std::mutex> lk(top->buildMu);
-    LinkMonitor* m = monitor_of(top, id);
-    if (!m) return -1;
-    compute_geometry(top);
-    // both ends on a vertex of the current attached set, as a timeline call
-    std::vector<int32_t> sc((size_t)n), dc((size_t)n);
-    for (int64_t i = 0; i < n; i++) {
-        const int32_t s = vertex_of_ip(top, srcIP[i]), d = vertex_of_ip(top, dstIP[i]);
-        sc[(size_t)i] = s >= 0 && s < top->g.V ? top->colOf[(size_t)s] : -1;
-        dc[(size_t)i] = d >= 0 && d < top->g.V ? top->colOf[(size_t)d] : -1;
-    }
-    return monitor_feed_cols(top, *m, sc, dc, weight, now, delivered, n);
-}
-
-int64_t shdtopo_monitor_feed_vertices(Topology* top, int id, const int32_t* srcVertex,
-                                      const int32_t* dstVertex, const uint64_t* weight,
-                                      const uint64_t* now, const uint8_t* delivered, int64_t n) {
-    if (!top || n < 0 || n > 0x7FFFFFFE) return -1;
-    if (n > 0 && (!srcVertex || !dstVertex)) return -1;
-    std::lock_guard<std::mutex> lk(top->buildMu);
-    LinkMonitor* m = monitor_of(top, id);
-    if (!m) return -1;
-    compute_geometry(top);
-    std::vector<int32_t> sc((size_t)n), dc((size_t)n);
-    for (int64_t i = 0; i < n; i++) {
-        const int32_t s = srcVertex[i], d = dstVertex[i];
-        sc[(size_t)i] = s >= 0 && s < top->g.V ? top->colOf[(size_t)s] : -1;
-        dc[(size_t)i] = d >= 0 && d < top->g.V ? top->colOf[(size_t)d] : -1;
-    }
-    return monitor_feed_cols(top, *m, sc, dc, weight, now, delivered, n);
-}
-
-int shdtopo_monitor_feed_device(Topology* top, int id, const int32_t* d_srcCol,
-                                const int32_t* d_dstCol, const uint32_t* d_payload,
-                                const uint64_t* d_now, const uint8_t* d_delivered, int64_t n,
-                                void* stream) {
-    if (!top || n < 0) return -1;
-    if (n > 0 && (!d_srcCol || !d_dstCol)) return -1;
-    std::lock_guard<std::mutex> lk(top->buildMu);
-    LinkMonitor* m = monitor_of(top, id);
-    if (!m) return -1;
-    m->st.feeds++;
-    if (m->rows == 0 || n == 0) return 0;
-    const int64_t rr = monitor_ready(top, *m);
-    if (rr < 0) return (int)rr;
-    int r = monitor_dev(top, *m);
-    if (r) return r;
-    r = monitor_dev_index(top, *m);
-    if (r) return r;
-    m->lastHostForm = false;
-    hipStream_t st = stream ? (hipStream_t)stream : top->stream;
-    return monitor_launch(top, *m, d_srcCol, d_dstCol, d_payload, nullptr,
-                          (const unsigned long long*)d_now, d_delivered, n, st);
-}
-
-int shdtopo_monitor_read(Topology* top, int id, uint64_t* bins, uint64_t* outside) {
-    if (!top) return -1;
-    std::lock_guard<std::mutex> lk(top->buildMu);
-    LinkMonitor* m = monitor_of(top, id);
-    if (!m) return -1;
-    int r = monitor_sync(top, *m);
-    if (r) return r;
-    const size_t nacc = m->nacc(), nb = (size_t)(m->rows * m->nbins);
-    std::vector<unsigned long long> acc(nacc, 0ull);
-    if (m->devBins && nacc)
-        HIPCHK(hipMemcpy(acc.data(), m->d_acc.p, 8 * nacc, hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < m->h_acc.size(); k++) acc[k] += m->h_acc[k];
-    if (bins) std::copy(acc.begin(), acc.begin() + (std::ptrdiff_t)nb, bins);
-    if (outside) std::copy(acc.begin() + (std::ptrdiff_t)nb, acc.end(), outside);
-    return 0;
-}
-
-int shdtopo_monitor_reset(Topology* top, int id) {
-    if (!top) return -1;
-    std::lock_guard<std::mutex> lk(top->buildMu);
-    LinkMonitor* m = monitor_of(top, id);
-    if (!m) return -1;
-    int r = monitor_sync(top, *m);
-    if (r) return r;
-    if (m->devBins) {
-        HIPCHK(hipMemsetAsync(m->d_acc.p, 0, 8 * std::max<size_t>(1, m->nacc()), top->stream));
-        HIPCHK(hipMemsetAsync(m->d_cnt.p, 0, 8 * 2 * MN_COUNT, top->stream));
-        HIPCHK(hipStreamSynchronize(top->stream));
-    }
-    std::fill(m->h_acc.begin(), m->h_acc.end(), (uint64_t)0);
-    std::fill(m->hcum, m->hcum + MN_COUNT, (int64_t)0);
-    std::fill(m->hlast, m->hlast + MN_COUNT, (int64_t)0);
-    m->unattachedCum = 0;
-    return 0;
-}
-
-int shdtopo_monitor_stats(Topology* top, int id, ShdMonitorStats* out) {
-    if (!top || !out) return -1;
-    std::lock_guard<std::mutex> lk(top->buildMu);
-    LinkMonitor* m = monitor_of(top, id);
-    if (!m) return -1;
-    int r = monitor_sync(top, *m);
-    if (r) return r;
-    unsigned long long dc[2 * MN_COUNT] = {};
-    if (m->devBins) HIPCHK(hipMemcpy(dc, m->d_cnt.p, sizeof dc, hipMemcpyDeviceToHost));
-    ShdMonitorStats& s = m->st;
-    if (m->timed) {  // taken lazily: the feed itself never waits
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, m->ek0, m->ek1));
-        s.feed_kernel_ms = ms;
-    } else {
-        s.feed_kernel_ms = 0;
-    }
-    auto cum = [&](int i) { return m->hcum[i] + (int64_t)dc[i]; };
-    s.in_range = cum(MN_IN);
-    s.before = cum(MN_BEFORE);
-    s.after = cum(MN_AFTER);
-    s.hits = s.in_range + s.before + s.after;
-    s.flows_hit = cum(MN_FLOWS);
-    s.fed = cum(MN_FED);
-    s.skipped_undelivered = cum(MN_SKIPPED);
-    s.unattached = m->hcum[MN_BAD] + m->unattachedCum;
-    s.bad_columns = (int64_t)dc[MN_BAD] - m->unattachedCum;
-    auto last = [&](int i) {
-        return m->lastOnDevice ? (int64_t)dc[MN_COUNT + i] : m->hlast[i];
-    };
-    s.last_in_range = last(MN_IN);
-    s.last_before = last(MN_BEFORE);
-    s.last_after = last(MN_AFTER);
-    s.last_hits = s.last_in_range + s.last_before + s.last_after;
-    s.last_flows_hit = last(MN_FLOWS);
-    s.last_fed = last(MN_FED);
-    s.last_skipped_undelivered = last(MN_SKIPPED);
-    s.last_unattached = m->lastHostForm ? last(MN_BAD) : 0;
-    s.last_bad_columns = m->lastHostForm ? 0 : last(MN_BAD);
-    *out = s;
-    return 0;
-}
-
-int64_t shdtopo_monitor_export_index(Topology* top, int id, int64_t* pairOff, int32_t* row,
-                                     uint64_t* offNs, int64_t cap) {
-    if (!top || cap < 0) return -1;
-    std::lock_guard<std::mutex> lk(top->buildMu);
-    LinkMonitor* m = monitor_of(top, id);
-    if (!m) return -1;
-    int r = monitor_sync(top, *m);
-    if (r) return r;
-    if (m->rows == 0) return 0;
-    const int64_t rr = monitor_ready(top, *m);
-    if (rr < 0) return rr;
-    const int64_t nrec = m->nrec;
-    if (cap < nrec) return nrec;
-    const size_t noff = (size_t)(m->A * m->A + 1);
-    std::vector<MonRec> rec;
-    const MonRec* hr = m->h_rec.data();
-    if (!top->isComplete) {
-        rec.resize((size_t)nrec);
-        if (nrec)
-            HIPCHK(hipMemcpy(rec.data(), m->d_rec.p, sizeof(MonRec) * (size_t)nrec,
-                             hipMemcpyDeviceToHost));
-        hr = rec.data();
-        if (pairOff) HIPCHK(hipMemcpy(pairOff, m->d_off.p, 8 * noff, hipMemcpyDeviceToHost));
-    } else if (pairOff) {
-        std::copy(m->h_off.begin(), m->h_off.end(), pairOff);
-    }
-    for (int64_t k = 0; k < nrec; k++) {
-        if (row) row[k] = (int32_t)hr[k].row;
-        if (offNs) offNs[k] = hr[k].offNs;
-    }
-    return nrec;
-}
-
-int64_t shdtopo_format_route(Topology* top, const ShdRoute* r, const int32_t* vertices,
-                             const int32_t* edges, char* buf, size_t cap) {
-    if (!top || !r || !vertices || !edges || (cap > 0 && !buf)) return -1;
-    if (r->status != kTraceOk || r->offset < 0 || r->hops < 1) return -1;
-    const HostGraph& g = top->g;
-    const int32_t* v = vertices + r->offset;
-    const int32_t* e = edges + r->offset;
-    const int64_t h = r->hops;
-    for (int64_t k = 0; k <= h; k++)
-        if (v[k] < 0 || v[k] >= g.V) return -1;
-    for (int64_t k = 0; k < h; k++)
-        if (e[k] < 0 || (int64_t)e[k] >= g.E) return -1;
-    // shd-topology.c:594,644,654-656
-    char num[400];
-    std::string path = g.vid[(size_t)v[0]];
-    for (int64_t k = 0; k < h; k++) {
-        snprintf(num, sizeof num, "--[%f,%f]-->", g.elat[(size_t)e[k]], 1.0 - g.eloss[(size_t)e[k]]);
-        path += num;
-        path += g.vid[(size_t)v[k + 1]];
-    }
-    std::string out = "shortest path " + g.vid[(size_t)v[0]] + "-->" + g.vid[(size_t)v[h]];
-    snprintf(num, sizeof num, " (%i-->%i) is %f ms", (int)v[0], (int)v[h], r->latency);
-    out += num;
-    snprintf(num, sizeof num, " with %f loss, path: ", 1.0 - r->reliability);
-    out += num;
-    out += path;
-    if (cap > 0) {
-        const size_t c = std::min(out.size(), cap - 1);
-        memcpy(buf, out.data(), c);
-        buf[c] = 0;
-    }
-    return (int64_t)out.size();
-}
-
 int64_t shdtopo_export_csr(Topology* top, int32_t* perm, uint32_t* rowptr, uint32_t* col,
                            double* pot, uint32_t* treeParent) {
     if (!top) return -1;
@@ -6588,10 +4066,7 @@ int64_t shdtopo_table_diff(Topology* a, Topology* b, ShdTableChange* out, int64_
 }
 
 int shdtopo_table_diff_stats(Topology* a, ShdDiffStats* out) {
-    if (!a || !out) return -1;
-    std::lock_guard<std::mutex> lk(a->buildMu);
-    *out = a->diffStats;
-    return 0;
+    return copy_stats(a, &_Topology::diffStats, out);
 }
 
 int shdtopo_synth_packets(Topology* top, uint64_t seed, int64_t n_hosts, int64_t n_packets,

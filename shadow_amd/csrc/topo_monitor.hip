@@ -123,7 +123,7 @@ monitor_offsets_kernel(const int64_t* __restrict__ in, int64_t* __restrict__ out
 struct FeedCount {
     u64 in = 0, before = 0, after = 0, flows = 0, fed = 0, skipped = 0, bad = 0;
 };
-// TimelineOut::add (topo_core.cpp) / bin_add (topo_timeline.hip): weight w of row `row` at time t
+// TimelineOut::add (topo_flows.cpp) / bin_add (topo_timeline.hip): weight w of row `row` at time t
 __device__ __forceinline__ void bin_add(const TimeBins& tb, int64_t row, u64 t, u64 w,
                                         FeedCount& fc) {
     if ((uint64_t)row >= (uint64_t)tb.rows) return;  // (the index rows are below rows)

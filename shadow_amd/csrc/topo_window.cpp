@@ -10,14 +10,11 @@
 #include <vector>
 
 #include "../../include/shd_topology_window.h"
+#include "topo_host.h"
 
 extern "C" {
 __attribute__((weak)) uint32_t address_toNetworkIP(Address* address);
 __attribute__((weak)) double random_nextDouble(Random* random);
-// src/support/shd-logging.h:122-124, as topo_core.cpp imports it
-__attribute__((weak)) void logging_log(const char* log_domain, int log_level, const char* fileName,
-                                       const char* functionName, int lineNumber,
-                                       const char* format, ...);
 }
 
 // One recorded packet: its vertices are resolved at emit, when the reference routed it
@@ -149,16 +146,9 @@ int topowindow_flush(TopoWindow* w, uint64_t jumpNs, int multiThreaded, TopoWind
         const int64_t fr = shdtopo_monitor_feed_vertices(w->top, monitor, sv.data(), dv.data(),
                                                          bytes ? wt.data() : nullptr, now.data(),
                                                          dl.data(), (int64_t)n);
-        if (fr < 0) {
-            if (logging_log)
-                logging_log("shadow", 1 << 4, __FILE__, __FUNCTION__, __LINE__,
-                            "link monitor %d: feeding a window of %lld packets failed: %lld",
-                            monitor, (long long)n, (long long)fr);
-            else if (!getenv("SHDTOPO_LOG") || atoi(getenv("SHDTOPO_LOG")) >= 1)
-                fprintf(stderr,
-                        "[shdtopo] warning: link monitor %d: feeding a window of %lld packets "
-                        "failed: %lld\n", monitor, (long long)n, (long long)fr);
-        }
+        if (fr < 0)
+            WARNING("link monitor %d: feeding a window of %lld packets failed: %lld", monitor,
+                    (long long)n, (long long)fr);
     }
     // the window's packets are routed: vertices detached during it may leave the table now
     shdtopo_window_release(w->top);
