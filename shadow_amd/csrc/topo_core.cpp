@@ -11,7 +11,6 @@
 //     for the same query sequence;
 //   * attach uses a candidate index built once instead of an O(V) scan per host.
 #include <arpa/inet.h>
-#include <dlfcn.h>
 
 #include <condition_variable>
 #include <cstdarg>
@@ -102,9 +101,7 @@ uint64_t next_topology_uid() {
     return n.fetch_add(1) + 1;
 }
 
-// (external linkage: topo_host.h declares what topo_flows.cpp and topo_monitor_host.cpp call)
-void edge_scan(Topology* top);
-
+// (external linkage: topo_host.h declares what the other host units call)
 void fatal_or_continue(Topology* top, const char* what) {
     CRITICAL("%s", what);
     if (top->abortOnError) abort();
@@ -404,13 +401,6 @@ int upload_csr(Topology* top) {
     top->stats.csr_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return r;
 }
-
-// Hubs of the tail grouping: the tail is grouped by its highest-ranked neighbour
-// among the first kGroupHubs vertices of the degree order (the count the former single-source
-// kernel held in LDS, where the grouping was tuned).
-constexpr int64_t kGroupHubs = 16565;
-// sample rows of the tie probe (enqueue_rows): 8 batches of 8, one short launch
-constexpr int64_t kTieProbeRows = 64;
 
 // Graph preparation.  Topologies are prepared on the GPU
 // (topo_prep.hip): the parsed edge arrays are copied to HBM once, and the relabel, the CSR, the
@@ -1074,821 +1064,6 @@ SsspLdsPlan batch_lds_plan(Topology* top, int K) {
         top->g.V);
 }
 
-// The batch layout of a launch goes to the device: output row (rowmap) and source of each
-// position, its bucket shift sh = C - d(src, h0) >= 2 delta (every source's h0 at C, h0_shift;
-// topo_sssp_batch.hip), and the batch starts of a measured layout.
-int upload_layout(Topology* top, const std::vector<uint32_t>& src, const std::vector<uint32_t>& perm,
-                  const std::vector<uint32_t>* bstart, double delta, hipStream_t st) {
-    const int64_t rows = (int64_t)src.size();
-    std::vector<uint32_t>& psrc = top->layPsrc;
-    psrc.resize((size_t)rows);
-    for (int64_t i = 0; i < rows; i++) psrc[(size_t)i] = src[(size_t)perm[(size_t)i]];
-    HIPCHK(top->d_rowmap.ensure((size_t)rows));
-    HIPCHK(top->d_bsrc.ensure((size_t)rows));
-    HIPCHK(hipMemcpyAsync(top->d_rowmap.p, perm.data(), 4 * (size_t)rows, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(top->d_bsrc.p, psrc.data(), 4 * (size_t)rows, hipMemcpyHostToDevice, st));
-    const std::vector<double> sh = source_shifts(top, psrc.data(), rows, delta);
-    HIPCHK(top->d_srcsh.ensure((size_t)rows));
-    HIPCHK(hipMemcpyAsync(top->d_srcsh.p, sh.data(), sizeof(double) * (size_t)rows,
-                          hipMemcpyHostToDevice, st));
-    const std::vector<double> hs = source_h0_seeds(top, psrc.data(), rows);
-    HIPCHK(top->d_h0seed.ensure((size_t)rows));
-    HIPCHK(hipMemcpyAsync(top->d_h0seed.p, hs.data(), sizeof(double) * (size_t)rows,
-                          hipMemcpyHostToDevice, st));
-    if (bstart) {
-        HIPCHK(top->d_bstart.ensure(bstart->size()));
-        HIPCHK(hipMemcpyAsync(top->d_bstart.p, bstart->data(), 4 * bstart->size(),
-                              hipMemcpyHostToDevice, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));  // perm / sh / hs / bstart must outlive the copies
-    return 0;
-}
-
-// the kernel's contract (topo_sssp_batch.hip): runs of 1..K positions covering [0, rows)
-static bool check_runs(const std::vector<uint32_t>& lstart, int64_t rows, int K) {
-    if (lstart.size() < 2 || lstart.front() != 0u || lstart.back() != (uint32_t)rows) return false;
-    for (size_t b = 0; b + 1 < lstart.size(); b++)
-        if (lstart[b + 1] <= lstart[b] || lstart[b + 1] - lstart[b] > (uint32_t)K) return false;
-    return true;
-}
-
-// Measured batch layout (option balance).  A batch's wall time is modelled
-// as a fixed part a plus its sources' costs; both come from the batch times of earlier launches
-// on this graph (record_costs).  Once every source of the rows has a cost:
-//  * one round of the slots (an 8-GPU shard): the grouping order (source_order) is cut into at
-//    most `slots` runs of <= K consecutive positions minimising the largest predicted batch
-//    (greedy cuts under a bisected bound) -- batches stay runs of the grouping, so the sources
-//    that share expansions stay together, but a run of expensive sources gets fewer of them;
-//  * several rounds: batches of kf in the grouping order, dequeued longest predicted first (the
-//    dynamic dequeue is then list scheduling in LPT order), the ragged batch last.
-// The layout changes only which batch computes a row: every row is the same (bit-exact tests).
-// A re-cut from the updated costs each build beat refining the previous cut (moving edge sources
-// off the slowest batches): a batch's time repeats within ~0.3 ms for the same sources but is
-// predicted from other compositions only loosely (corr 0.4-0.7), and both end near 11 ms at 1,250
-// rows.
-// The layout from the costs c (per position of the grouping order) and the fixed part a: `order`
-// lists the grouping positions in launch order, `lstart` the batch starts (shdtopo_test_batch_layout
-// exposes it to the CPU tests).
-static bool layout_from_costs(const std::vector<double>& c, double a, int kf, int slots, int K,
-                              std::vector<uint32_t>& order, std::vector<uint32_t>& lstart) {
-    const int64_t rows = (int64_t)c.size();
-    if (rows < 1 || kf < 1 || kf > K || slots < 1) return false;
-    const int64_t nplain = (rows + kf - 1) / kf;
-    order.resize((size_t)rows);
-    std::iota(order.begin(), order.end(), 0u);
-    lstart.clear();
-    if (nplain <= (int64_t)slots) {
-        // the fewest runs whose predicted cost stays <= B (greedy is optimal for a bound)
-        auto cut = [&](double B, std::vector<uint32_t>* out) -> int64_t {
-            int64_t n = 0, i = 0;
-            if (out) out->push_back(0u);
-            while (i < rows) {
-                double s = a;
-                int m = 0;
-                while (i < rows && m < K && (m == 0 || s + c[(size_t)i] <= B)) {
-                    s += c[(size_t)i];
-                    i++;
-                    m++;
-                }
-                n++;
-                if (out) out->push_back((uint32_t)i);
-            }
-            return n;
-        };
-        double lo = a, hi = a;
-        for (int64_t b = 0; b < nplain; b++) {  // the plain layout's largest batch: feasible
-            double s = a;
-            for (int64_t i = b * kf; i < std::min(rows, (b + 1) * kf); i++) s += c[(size_t)i];
-            hi = std::max(hi, s);
-        }
-        for (int64_t i = 0; i < rows; i++) lo = std::max(lo, a + c[(size_t)i]);
-        if (cut(hi, nullptr) > (int64_t)slots) return false;
-        for (int it = 0; it < 40 && hi - lo > 1e-4 * hi; it++) {
-            const double mid = 0.5 * (lo + hi);
-            if (cut(mid, nullptr) <= (int64_t)slots) hi = mid;
-            else lo = mid;
-        }
-        cut(hi, &lstart);
-    } else {
-        std::vector<double> bc((size_t)nplain, a);
-        for (int64_t i = 0; i < rows; i++) bc[(size_t)(i / kf)] += c[(size_t)i];
-        std::vector<uint32_t> bo((size_t)nplain);
-        std::iota(bo.begin(), bo.end(), 0u);
-        const bool ragged = rows % kf != 0;
-        std::stable_sort(bo.begin(), bo.end() - (ragged ? 1 : 0),
-                         [&](uint32_t x, uint32_t y) { return bc[x] > bc[y]; });
-        order.clear();
-        lstart.push_back(0u);
-        for (uint32_t b : bo) {
-            for (int64_t i = (int64_t)b * kf; i < std::min(rows, ((int64_t)b + 1) * kf); i++)
-                order.push_back((uint32_t)i);
-            lstart.push_back((uint32_t)order.size());
-        }
-    }
-    return check_runs(lstart, rows, K);
-}
-
-bool measured_layout(Topology* top, const std::vector<uint32_t>& src, int kf, int slots,
-                     std::vector<uint32_t>& lperm, std::vector<uint32_t>& lstart) {
-    const int64_t rows = (int64_t)src.size();
-    const std::vector<uint32_t>& base = top->ordBase;
-    if (top->costHp != top->hp.get() || (int64_t)base.size() != rows || rows < 2) return false;
-    std::vector<double> c((size_t)rows);
-    for (int64_t i = 0; i < rows; i++) {
-        const float x = top->srcCost[(size_t)src[(size_t)base[(size_t)i]]];
-        if (!(x > 0.0f)) return false;
-        c[(size_t)i] = (double)x;
-    }
-    std::vector<uint32_t> order;
-    if (!layout_from_costs(c, top->costA, kf, slots, batch_k(top), order, lstart)) return false;
-    lperm.resize((size_t)rows);
-    for (int64_t i = 0; i < rows; i++) lperm[(size_t)i] = base[(size_t)order[(size_t)i]];
-    return true;
-}
-
-// Costs from a launch's batch times (SlotWs::btrace: dequeue and end ticks per batch): the
-// fixed part a = 1/3 of the mean batch (C4: a lone source takes 4.3 ms, a batch of 5 8.9 ms,
-// of 8 10.2 ms), the rest shared equally by the batch's sources; both averaged with the earlier
-// builds' (weight 1/2), so a source that moves to another batch converges to its own share.
-void record_costs(Topology* top, const std::vector<uint32_t>& psrc, const std::vector<uint32_t>& lstart,
-                  const std::vector<unsigned long long>& bt) {
-    const int64_t nb = (int64_t)lstart.size() - 1;
-    if (nb < 1) return;
-    if (top->balance == 2 && top->costHp == top->hp.get()) return;  // frozen (diagnostic)
-    if (top->costHp != top->hp.get() || (int64_t)top->srcCost.size() != top->g.V) {
-        top->srcCost.assign((size_t)top->g.V, 0.0f);
-        top->costHp = top->hp.get();
-        top->costA = 0.0;
-    }
-    std::vector<double> T((size_t)nb, 0.0);
-    double sum = 0.0;
-    int64_t n = 0;
-    for (int64_t b = 0; b < nb; b++) {
-        const unsigned long long t0 = bt[(size_t)b * kBTraceWords], t1 = bt[(size_t)b * kBTraceWords + 1];
-        if (t1 > t0) {
-            T[(size_t)b] = (double)(t1 - t0);
-            sum += T[(size_t)b];
-            n++;
-        }
-    }
-    if (n == 0) return;
-    const double mean = sum / (double)n, a = mean / 3.0;
-    top->costA = top->costA > 0.0 ? 0.5 * (top->costA + a) : a;
-    for (int64_t b = 0; b < nb; b++) {
-        if (!(T[(size_t)b] > 0.0)) continue;
-        const uint32_t p0 = lstart[(size_t)b], p1 = lstart[(size_t)b + 1];
-        const double cs = std::max(0.01 * mean, (T[(size_t)b] - a) / (double)(p1 - p0));
-        for (uint32_t p = p0; p < p1 && p < psrc.size(); p++) {
-            float& x = top->srcCost[(size_t)psrc[p]];
-            x = x > 0.0f ? (float)(0.5 * ((double)x + cs)) : (float)cs;
-        }
-    }
-}
-
-// wall checkpoints of a whole-table build (ShdStats.build_step_ms): the time since the previous
-// mark goes to step i
-void bstep_mark(Topology* top, int i) {
-    const auto t = std::chrono::steady_clock::now();
-    top->stats.build_step_ms[i] += std::chrono::duration<double, std::milli>(t - top->bstepT).count();
-    top->bstepT = t;
-}
-
-// per-build cold-path timings start at 0: a build that finds the graph (or the target set)
-// already prepared reports 0 for that step
-void reset_build_stats(Topology* top) {
-    top->stats.csr_ms = top->stats.csr_host_ms = top->stats.csr_copy_ms = 0.0;
-    top->stats.order_ms = top->stats.replay_prep_ms = top->stats.target_prep_ms = 0.0;
-    top->stats.batch_layout_measured = 0;
-    top->lastBatches = 0;
-    top->stats.workspace_ms = 0.0;
-    top->stats.csr_host_runs = 0;
-    top->stats.tie_probe_rows = top->stats.tie_probe_flagged = 0;
-    top->stats.tie_probe_ms = 0.0;
-}
-
-// The target-aware re-sort's scratch for the prepared relaxation copy (allocated once).
-// The long rows' entries for the segmented sort's device-wide radix sort (SegBig): positions
-// row by row, each entry's row ordinal, and the sort's end bit.
-void plan_long_rows(const uint32_t* rowptr, int64_t V, std::vector<uint32_t>& pos,
-                    std::vector<uint32_t>& row, int* end_bit) {
-    pos.clear();
-    row.clear();
-    uint32_t nrow = 0;
-    for (int64_t v = 0; v < V; v++) {
-        const uint32_t b = rowptr[v], e = rowptr[v + 1];
-        if (e - b <= kSegBlock) continue;
-        for (uint32_t p = b; p < e; p++) {
-            pos.push_back(p);
-            row.push_back(nrow);
-        }
-        nrow++;
-    }
-    int bits = 1;
-    while (bits < 31 && (1u << bits) < nrow) bits++;
-    *end_bit = 32 + bits;
-}
-
-int ensure_kprime_scratch(Topology* top, KprimeScratch* out) {
-    const int64_t nadj = (int64_t)(top->d_adjk.n / 4), V = top->g.V;
-    if (top->kpBig < 0) {
-        // the long rows (the graph's rows never change: listed once, in the preparation)
-        std::vector<uint32_t> rp((size_t)V + 1), pos, row;
-        HIPCHK(hipMemcpyAsync(rp.data(), top->d_rowptr.p, 4 * ((size_t)V + 1), hipMemcpyDeviceToHost,
-                              top->stream));
-        HIPCHK(hipStreamSynchronize(top->stream));
-        plan_long_rows(rp.data(), V, pos, row, &top->kpBigBits);
-        const size_t nb = pos.size();
-        HIPCHK(top->d_kpBigPos.ensure(std::max<size_t>(1, nb)));
-        HIPCHK(top->d_kpBigRow.ensure(std::max<size_t>(1, nb)));
-        HIPCHK(top->d_kpBigKey.ensure(std::max<size_t>(1, 2 * nb)));
-        HIPCHK(top->d_kpBigVal.ensure(std::max<size_t>(1, 2 * nb)));
-        if (nb) {
-            HIPCHK(hipMemcpyAsync(top->d_kpBigPos.p, pos.data(), 4 * nb, hipMemcpyHostToDevice, top->stream));
-            HIPCHK(hipMemcpyAsync(top->d_kpBigRow.p, row.data(), 4 * nb, hipMemcpyHostToDevice, top->stream));
-            HIPCHK(hipStreamSynchronize(top->stream));
-        }
-        top->kpBig = (int64_t)nb;
-    }
-    size_t tb = 0;
-    HIPCHK(segsort_big_tmp_bytes(top->kpBig, top->kpBigBits, &tb));
-    const size_t n = (size_t)std::max<int64_t>(1, nadj);
-    HIPCHK(top->d_kpKey.ensure(n));
-    HIPCHK(top->d_kpIdx.ensure(n));
-    HIPCHK(top->d_kpRec.ensure(n));
-    HIPCHK(top->d_kpTmp.ensure(std::max<size_t>(1, tb)));
-    if (out) {
-        out->key = top->d_kpKey.p;
-        out->idx = top->d_kpIdx.p;
-        out->rec = top->d_kpRec.p;
-        SegBig& b = out->big;
-        b.pos = top->d_kpBigPos.p;
-        b.row = top->d_kpBigRow.p;
-        b.nitems = top->kpBig;
-        b.end_bit = top->kpBigBits;
-        b.keys = top->d_kpBigKey.p;
-        b.vals = top->d_kpBigVal.p;
-        b.tmp = top->d_kpTmp.p;
-        b.tmp_bytes = top->d_kpTmp.n;
-    }
-    return 0;
-}
-
-// Enqueue rows [row0,row1) into out buffers (device pointers) on `st`.
-int enqueue_rows(Topology* top, int64_t row0, int64_t row1, double2* out_lr, uint16_t* out_hops,
-                 double* out_rowmin, hipStream_t st) {
-    const int64_t A = top->A;
-    const int64_t rows = row1 - row0;
-    if (rows <= 0 || A <= 0) return 0;
-    HIPCHK(hipMemsetAsync(top->d_stats.p, 0, sizeof(unsigned long long) * ST_COUNT, st));
-    HIPCHK(launch_fill_u64(top->d_stats.p + ST_GLOBAL_MIN, 0x7FF0000000000000ull, 1, st));
-    if (top->isComplete) {
-        // dense A x A direct-edge matrices (lowest edge id wins, as orc_get_eid), resident in HBM
-        // while the columns stay: rebuilt only when the attached set changed
-        if (top->aaCols != top->attached || !top->d_elatAA.p || !top->d_vlossA.p) {
-            std::vector<double> elat((size_t)(A * A), -1.0), eloss((size_t)(A * A), 0.0), vl((size_t)A);
-            const HostGraph& g = top->g;
-            for (int64_t e = 0; e < g.E; e++) {
-                int32_t ca = top->colOf[(size_t)g.eu[(size_t)e]], cb = top->colOf[(size_t)g.ev[(size_t)e]];
-                if (ca < 0 || cb < 0) continue;
-                size_t k1 = (size_t)ca * (size_t)A + (size_t)cb;
-                if (elat[k1] < 0) { elat[k1] = g.elat[(size_t)e]; eloss[k1] = g.eloss[(size_t)e]; }
-                if (!g.directed) {
-                    size_t k2 = (size_t)cb * (size_t)A + (size_t)ca;
-                    if (elat[k2] < 0) { elat[k2] = g.elat[(size_t)e]; eloss[k2] = g.eloss[(size_t)e]; }
-                }
-            }
-            for (int64_t i = 0; i < A; i++) vl[(size_t)i] = g.vloss[(size_t)top->attached[(size_t)i]];
-            HIPCHK(top->d_elatAA.ensure((size_t)(A * A)));
-            HIPCHK(top->d_elossAA.ensure((size_t)(A * A)));
-            HIPCHK(top->d_vlossA.ensure((size_t)A));
-            HIPCHK(hipMemcpyAsync(top->d_elatAA.p, elat.data(), sizeof(double) * (size_t)(A * A), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(top->d_elossAA.p, eloss.data(), sizeof(double) * (size_t)(A * A), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(top->d_vlossA.p, vl.data(), sizeof(double) * (size_t)A, hipMemcpyHostToDevice, st));
-            HIPCHK(hipStreamSynchronize(st));  // the host vectors must outlive the async copies
-            top->aaCols = top->attached;
-            top->stats.pair_matrix_builds++;
-        }
-        // one launch: records, hops, row minima and the global minimum
-        HIPCHK(hipEventRecord(top->ev0, st));
-        HIPCHK(launch_pair_table_complete((int)A, row0, rows, top->d_elatAA.p, top->d_elossAA.p,
-                                          top->d_vlossA.p, out_lr, out_hops, out_rowmin,
-                                          top->d_stats.p, st));
-        HIPCHK(hipEventRecord(top->ev1, st));
-    } else {
-        int r = upload_csr(top);
-        if (r) return r;
-        // the "replay_all" test hook runs every row through the exact heap replay; otherwise
-        // the batch kernel runs (directed topologies too: out-rows relaxed, parents from the
-        // in-rows) and flags the rows that need it
-        // multigraphs too: the reference sums the igraph_get_eid edge of each hop, which the batch
-        // epilogue (latency = distance) does not reproduce when parallel edges differ
-        const bool dense = top->tieReplay && (top->tieDenseOpt == 1 ||
-                                              (top->tieDenseOpt < 0 && top->tieDense));
-        const bool allReplay = top->replayAll || top->hasMultiEdges || dense;
-        bool probeDense = false;  // the tie probe below found the topology tie-dense
-        // the batched launch's per-batch times, read back after its closing event: its batch
-        // starts, fill (0: measured layout), slots and the SHD_BATCH_TRACE file
-        struct {
-            std::vector<uint32_t> start;
-            int kf = 0, slots = 0;
-            const char* file = nullptr;
-        } bt;
-        std::vector<uint32_t> src((size_t)rows), tgt((size_t)A);
-        for (int64_t i = 0; i < rows; i++) src[(size_t)i] = (uint32_t)top->hp->inv[(size_t)top->attached[(size_t)(row0 + i)]];
-        for (int64_t i = 0; i < A; i++) tgt[(size_t)i] = (uint32_t)top->hp->inv[(size_t)top->attached[(size_t)i]];
-        HIPCHK(top->d_sources.ensure((size_t)rows));
-        HIPCHK(top->d_targets.ensure((size_t)A));
-        HIPCHK(hipMemcpyAsync(top->d_sources.p, src.data(), sizeof(uint32_t) * (size_t)rows, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(top->d_targets.p, tgt.data(), sizeof(uint32_t) * (size_t)A, hipMemcpyHostToDevice, st));
-        const int K = batch_k(top);
-        top->stats.peeled_targets = 0;
-        HIPCHK(hipEventRecord(top->ev0, st));
-        if (!allReplay) {
-            r = ensure_workspace(top, (int)rows);
-            if (r) return r;
-            HIPCHK(top->d_rowflag.ensure((size_t)rows));
-            HIPCHK(hipMemsetAsync(top->d_rowflag.p, 0, (size_t)rows, st));
-            SlotWs ws = slot_ws(top);
-            ws.rowflag = top->d_rowflag.p;
-            // The relaxation copy's target-derived content (bit 30 target marks, the records'
-            // target-aware kappa field, the rows re-sorted by it) belongs to one target set: a new
-            // set first restores the plain copy from d_adj (stale keys of an older set
-            // would cut rows that lead to the new targets), then prepares the new set if the
-            // target skip is on.
-            const int64_t nadjk = (int64_t)(top->d_adjk.n / 4);
-            // leaf targets: the records go with the launch, the copy's target-derived content
-            // with the effective set -- a copy prepared the other way is restored first
-            const bool leaf = leaf_targets_on(top);
-            if (leaf) {
-                r = ensure_leaf_targets(top, tgt, top->d_targets.p, st);
-                if (r) return r;
-                ws.tleaf = top->d_tleaf.p;
-            }
-            top->stats.peeled_targets = leaf ? top->leafPeeled : 0;
-            if (!top->adjkPlain && (top->adjkTargets != tgt || top->adjkLeaf != leaf)) {
-                HIPCHK(launch_kappa_copy(top->g.V, nadjk, hub_segs(top), top->d_rowptr.p, adj_out(top), top->d_pot.p,
-                                         top->d_sptPar.p, top->d_adjk.p, top->d_kap.p,
-                                         top->d_ksum.p, top->d_kap0.p, st));
-                top->adjkPlain = true;
-                top->adjkFlagged = false;
-                top->adjkResorted = false;
-                top->adjkLeaf = false;
-                top->adjkTargets.clear();
-            }
-            if (top->targetSkip && top->adjkPlain) {
-                // bit 30 of the relaxation copy's columns: the current target set.  Everything
-                // after the bit upload is enqueued without a host sync: the GPU prepares the
-                // target set while the host computes the source order below (the fixpoint always
-                // runs target_kappa iterations -- past its convergence an iteration reproduces its
-                // input bit for bit -- and each iteration's change flag is read afterwards).
-                r = upload_target_bits(top, tgt, st);
-                if (r) return r;
-                HIPCHK(hipEventRecord(top->evp0, st));
-                // (leaf targets: the effective set's bits, the peeled vertices dead)
-                const uint32_t* tbits = leaf ? top->d_tbitsEff.p : top->d_tbits.p;
-                const uint32_t* dead = leaf ? top->d_dead.p : nullptr;
-                HIPCHK(launch_mark_targets(top->d_adjk.p, nadjk, tbits, st));
-                // the records' kappa field: the target-aware fixpoint (kappa0 with 0 iterations)
-                const int64_t V = top->g.V;
-                const HubSegs hs = hub_segs(top);
-                const int nit = std::max(0, top->targetKappa);
-                HIPCHK(top->d_kfA.ensure(2 * (size_t)V));  // [K | Kt] (launch_kfix_step)
-                HIPCHK(top->d_kfB.ensure(2 * (size_t)V));
-                HIPCHK(top->d_kfPart.ensure(std::max<size_t>(1, hs.nseg)));
-                HIPCHK(top->d_kfChanged.ensure((size_t)nit + 1));
-                if (!top->kfKapReady) {  // the out-rows' static w - pi (once per graph)
-                    HIPCHK(top->d_kfKap.ensure((size_t)std::max<int64_t>(1, nadjk)));
-                    HIPCHK(launch_kfix_kap(adj_out(top), top->d_pot.p, nadjk, top->d_kfKap.p, st));
-                    top->kfKapReady = true;
-                }
-                HIPCHK(hipMemsetAsync(top->d_kfChanged.p, 0, sizeof(unsigned int) * ((size_t)nit + 1), st));
-                HIPCHK(launch_kfix_step(top->d_rowptr.p, adj_out(top), top->d_kfKap.p, tbits,
-                                        nullptr, top->d_kfA.p, V, hs, top->d_kfPart.p,
-                                        top->d_kfChanged.p, st, dead));
-                double* kin = top->d_kfA.p;
-                double* kout = top->d_kfB.p;
-                for (int it = 0; it < nit; it++) {
-                    HIPCHK(launch_kfix_step(top->d_rowptr.p, adj_out(top), top->d_kfKap.p,
-                                            tbits, kin, kout, V, hs, top->d_kfPart.p,
-                                            top->d_kfChanged.p + 1 + it, st, dead));
-                    std::swap(kin, kout);
-                }
-                if (top->targetResort) {
-                    KprimeScratch sc;
-                    r = ensure_kprime_scratch(top, &sc);
-                    if (r) return r;
-                    HIPCHK(launch_kprime_resort(top->d_adjk.p, top->d_kap.p, top->d_ksum.p,
-                                                top->d_kap0.p, top->d_rowptr.p, V, nadjk,
-                                                top->d_pot.p, tbits, kin, sc, st));
-                }
-                HIPCHK(launch_kfix_store(top->d_adjk.p, nadjk, kin, st));
-                top->kfFinal = kin;
-                HIPCHK(hipEventRecord(top->evp1, st));
-                top->tpPending = true;
-                top->adjkTargets = tgt;
-                top->adjkFlagged = true;
-                top->adjkLeaf = leaf;
-                top->adjkPlain = false;
-                top->adjkResorted = top->targetResort;
-            }
-            // Tie probe (integer latencies, before the first batched build of the topology):
-            // the batch kernel on kTieProbeRows sample rows (the range's first rows, written in
-            // place); if >= 90 % of them cross a d-tied parent the topology is tie-dense and
-            // every row goes straight to the heap replay -- the batch kernel would only compute
-            // rows the replay recomputes (C4-int: 0.93 s of batch kernel per first build).
-            if (top->tieReplay && top->tieDenseOpt < 0 && !top->tieDense && !top->tieProbed &&
-                rows >= 2 * kTieProbeRows) {
-                edge_scan(top);
-                if (top->replayIntOk) {
-                    top->tieProbed = true;
-                    const auto tq0 = std::chrono::steady_clock::now();
-                    const int64_t P = kTieProbeRows;
-                    const double delta = default_delta(top);
-                    const std::vector<double> sh = source_shifts(top, src.data(), P, delta);
-                    HIPCHK(top->d_probeSrc.ensure((size_t)P));
-                    HIPCHK(top->d_probeSh.ensure((size_t)P));
-                    HIPCHK(hipMemcpyAsync(top->d_probeSrc.p, src.data(), 4 * (size_t)P, hipMemcpyHostToDevice, st));
-                    HIPCHK(hipMemcpyAsync(top->d_probeSh.p, sh.data(), 8 * (size_t)P, hipMemcpyHostToDevice, st));
-                    const std::vector<double> hs = source_h0_seeds(top, src.data(), P);
-                    HIPCHK(top->d_probeSeed.ensure((size_t)P));
-                    HIPCHK(hipMemcpyAsync(top->d_probeSeed.p, hs.data(), 8 * (size_t)P, hipMemcpyHostToDevice, st));
-                    SlotWs pws = ws;
-                    pws.rowmap = nullptr;  // sample row i -> output row i
-                    const SsspLdsPlan bp = batch_lds_plan(top, K);
-                    r = hub_rows_ready(top, bp.H, st);
-                    if (r) return r;
-                    HIPCHK(launch_sssp_batch(K, dev_csr(top), pws, top->d_probeSrc.p, top->d_probeSh.p,
-                                             top->d_probeSeed.p, (int)P, K, top->d_targets.p, (int)A, delta, bp,
-                                             top->iterGuard, out_lr, out_hops, out_rowmin,
-                                             top->d_stats.p, st));
-                    std::vector<uint8_t> fl((size_t)P);
-                    HIPCHK(hipMemcpyAsync(fl.data(), top->d_rowflag.p, (size_t)P, hipMemcpyDeviceToHost, st));
-                    HIPCHK(hipStreamSynchronize(st));
-                    int64_t nf = 0;
-                    for (uint8_t x : fl) nf += x ? 1 : 0;
-                    top->stats.tie_probe_rows = P;
-                    top->stats.tie_probe_flagged = nf;
-                    if (nf * 10 >= P * 9) top->tieDense = true;
-                    // the build's statistics and row flags start over (the rows are recomputed)
-                    HIPCHK(hipMemsetAsync(top->d_stats.p, 0, sizeof(unsigned long long) * ST_COUNT, st));
-                    HIPCHK(launch_fill_u64(top->d_stats.p + ST_GLOBAL_MIN, 0x7FF0000000000000ull, 1, st));
-                    HIPCHK(hipMemsetAsync(top->d_rowflag.p, 0, (size_t)rows, st));
-                    HIPCHK(hipStreamSynchronize(st));
-                    top->stats.tie_probe_ms = std::chrono::duration<double, std::milli>(
-                        std::chrono::steady_clock::now() - tq0).count();
-                }
-            }
-            probeDense = top->tieReplay && top->tieDenseOpt < 0 && top->tieDense;
-            if (!probeDense) {
-                const auto to0 = std::chrono::steady_clock::now();
-                // sources per batch: a shard that leaves slots idle at K (8-GPU builds: 1250
-                // rows = 157 batches for 256 slots) spreads over every slot with fewer sources
-                // per batch (C4, 1250 rows: 89.7 -> 83.2 ms).  With more than one round it does
-                // not pay (2500 rows at 5 per batch: 146 -> 158 ms).
-                int kf = K;
-                if (top->batchFill > 0) {
-                    kf = std::min(K, top->batchFill);
-                } else {
-                    // the fewest sources per batch that still finish the rows in the fewest
-                    // rounds of the slots: a batch's time grows with its sources, so equal
-                    // rounds of smaller batches beat a last round of a few full ones (2,500
-                    // rows on 256 slots: 500 batches of 5, two even rounds, instead of 313
-                    // batches of 8 whose last 57 form a second round on their own)
-                    const int64_t S = std::max(1, ws.slots);
-                    const int64_t rounds = (rows + (int64_t)K * S - 1) / ((int64_t)K * S);
-                    kf = (int)std::max<int64_t>(1, std::min<int64_t>(K, (rows + rounds * S - 1) / (rounds * S)));
-                }
-                top->stats.batch_fill = kf;
-                // workgroups the launch uses: the batches, at most the workspace's slots (it
-                // may hold more: sized for a full table by the attach-time preparation)
-                top->slotsUsed = (int)std::min<int64_t>(ws.slots, (rows + kf - 1) / kf);
-                const double delta = default_delta(top);
-                // the order, the row map and the bucket shifts depend only on the sources, the
-                // batch fill and the options: a rebuild of the same rows reuses them
-                const int64_t nbat = (rows + kf - 1) / kf;
-                const int border = top->batchOrder != 5 ? top->batchOrder
-                                   : nbat > 3 * (int64_t)std::max(1, ws.slots) ? 4 : 2;
-                const bool cached = top->ordHp == top->hp.get() && top->ordKf == kf &&
-                                    top->ordSO == top->sourceOrder && top->ordBO == border &&
-                                    top->ordDelta == delta && top->ordPhase == h0_phase(top, delta) &&
-                                    top->ordSrc == src;
-                if (!cached) {
-                // Batches of K sources settle in lock-step and share an expansion when their
-                // shifted distances to a vertex fall in one bucket: sources whose shortest paths
-                // enter the hub core through the same hub share the most.  Batch position p takes
-                // source perm[p]; the kernel writes its row at rowmap[p] = perm[p].
-                std::vector<uint32_t> perm((size_t)rows);
-                std::iota(perm.begin(), perm.end(), 0u);
-                if (top->sourceOrder == 2) {
-                    // preorder of the h0 shortest-path tree (children by ascending vertex id):
-                    // sources in one subtree (sharing the longest path prefix from h0) are
-                    // adjacent.  Preorder = lexicographic order of the root-first parent paths;
-                    // the forest's preorder (HostPrep::preorder, from the graph preparation)
-                    // numbers h0's tree first, then the other roots' trees
-                    const std::vector<uint32_t>& pre = top->hp->preorder;
-                    std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) {
-                        return pre[src[a]] < pre[src[b]];
-                    });
-                } else if (top->sourceOrder == 1) {
-                    const uint32_t Hc = (uint32_t)std::min<int64_t>(kGroupHubs, top->g.V);
-                    std::vector<uint64_t> key((size_t)rows);
-                    for (int64_t i = 0; i < rows; i++) {
-                        uint32_t v = src[(size_t)i];
-                        for (int hop = 0; v >= Hc && hop < 64; hop++) {  // up the h0 tree
-                            const uint32_t p = top->hp->sptPar[(size_t)v];
-                            if (p == 0xFFFFFFFFu) break;
-                            v = p;
-                        }
-                        const double pi = top->hp->pot[(size_t)src[(size_t)i]];
-                        const float pf = std::isfinite(pi) ? (float)pi : INFINITY;
-                        uint32_t pb;
-                        memcpy(&pb, &pf, 4);
-                        key[(size_t)i] = ((uint64_t)v << 32) | pb;  // pi >= 0: bits order as values
-                    }
-                    std::stable_sort(perm.begin(), perm.end(),
-                                     [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
-                }
-                top->ordBase = perm;  // the grouping order (the measured layout starts from it)
-                // order of the batches (groups of kf consecutive positions) in the dequeue: the
-                // kernel ends with the slowest slot, so the last batches decide its tail
-                // batch_order 5 (auto): by depth when the batches fill more than 3 rounds of the
-                // slots -- longest-predicted first shortens the tail of a many-round launch (full
-                // table: 71.1 -> 68.5 ms) -- else by pi: with two rounds the order only pairs
-                // batches, and the depth predictor pairs them worse (2,500 rows: 25.9 -> 28.6 ms)
-                if (border != 0 && rows > kf) {
-                    const int64_t nb = nbat;
-                    std::vector<uint32_t> bo((size_t)nb);
-                    std::iota(bo.begin(), bo.end(), 0u);
-                    if (border == 1) {
-                        SplitMix rng(0x5eedull);
-                        for (int64_t i = nb - 1; i > 0; i--) std::swap(bo[(size_t)i], bo[(size_t)rng.below((uint64_t)i + 1)]);
-                    } else {
-                        std::vector<double> mp((size_t)nb, 0.0);
-                        for (int64_t b = 0; b < nb; b++) {
-                            int64_t c = 0;
-                            for (int64_t i = b * kf; i < std::min(rows, (b + 1) * kf); i++, c++) {
-                                const uint32_t s = src[(size_t)perm[(size_t)i]];
-                                if (border == 4) {
-                                    // the source's depth in the h0 shortest-path tree: deeper
-                                    // sources relax more pairs (C4: corr 0.59 with the batch's
-                                    // duration, against 0.25 for mean pi)
-                                    mp[(size_t)b] += (double)top->hp->depth[s];
-                                } else {
-                                    const double p = top->hp->pot[(size_t)s];
-                                    mp[(size_t)b] += std::isfinite(p) ? p : 0.0;
-                                }
-                            }
-                            mp[(size_t)b] /= (double)std::max<int64_t>(1, c);
-                        }
-                        const bool desc = border != 3;
-                        std::stable_sort(bo.begin(), bo.end(), [&](uint32_t a, uint32_t b) {
-                            return desc ? mp[a] > mp[b] : mp[a] < mp[b];
-                        });
-                    }
-                    // the ragged batch (if any) stays last
-                    const int64_t last = nb - 1;
-                    if (rows % kf) {
-                        auto it = std::find(bo.begin(), bo.end(), (uint32_t)last);
-                        bo.erase(it);
-                        bo.push_back((uint32_t)last);
-                    }
-                    std::vector<uint32_t> p2;
-                    p2.reserve((size_t)rows);
-                    for (uint32_t b : bo)
-                        for (int64_t i = (int64_t)b * kf; i < std::min(rows, ((int64_t)b + 1) * kf); i++)
-                            p2.push_back(perm[(size_t)i]);
-                    perm.swap(p2);
-                }
-                top->ordPerm.swap(perm);
-                top->ordSrc = src;
-                top->ordHp = top->hp.get();
-                top->ordKf = kf;
-                top->ordSO = top->sourceOrder;
-                top->ordBO = border;
-                top->ordDelta = delta;
-                top->ordPhase = h0_phase(top, delta);
-                top->ordUploaded = false;
-                }
-                // the launch's layout: batches sized and ordered by the sources' measured costs
-                // (option balance, once every source has one), else the cached order
-                std::vector<uint32_t> lperm, lstart;
-                const bool measured =
-                    top->balance && measured_layout(top, src, kf, ws.slots, lperm, lstart);
-                if (measured || !top->ordUploaded) {
-                    const std::vector<uint32_t>& perm = measured ? lperm : top->ordPerm;
-                    r = upload_layout(top, src, perm, measured ? &lstart : nullptr, delta, st);
-                    if (r) return r;
-                    top->ordUploaded = !measured;
-                }
-                if (!measured) {
-                    lstart.resize((size_t)nbat + 1);
-                    for (int64_t b = 0; b <= nbat; b++) lstart[(size_t)b] = (uint32_t)std::min(rows, b * kf);
-                }
-                ws.bstart = measured ? top->d_bstart.p : nullptr;
-                ws.nbat = measured ? (int)(lstart.size() - 1) : 0;
-                const int64_t lnbat = (int64_t)lstart.size() - 1;
-                top->slotsUsed = (int)std::min<int64_t>(ws.slots, lnbat);
-                top->stats.batch_layout_measured = measured ? 1 : 0;
-                top->lastBatches = lnbat;
-                ws.rowmap = top->d_rowmap.p;
-                // per batch {start tick, end tick, slot, near iterations, sweeps, expansions,
-                // relaxations, sources, ...} (kBTraceWords u64): the batch times give the sources'
-                // costs (option balance); SHD_BATCH_TRACE=<file> (diagnostic) appends them, then
-                // per batch position {source vertex, pi bits}
-                const char* btf = getenv("SHD_BATCH_TRACE");
-                if (top->balance || (btf && *btf)) {
-                    HIPCHK(top->d_btrace.ensure((size_t)lnbat * kBTraceWords));
-                    ws.btrace = top->d_btrace.p;
-                }
-                top->stats.order_ms = std::chrono::duration<double, std::milli>(
-                    std::chrono::steady_clock::now() - to0).count();
-                HIPCHK(hipEventRecord(top->ev0, st));
-                const SsspLdsPlan bp = batch_lds_plan(top, K);
-                top->stats.lds_hubs = bp.H;
-                r = hub_rows_ready(top, bp.H, st);
-                if (r) return r;
-                bstep_mark(top, 2);
-                HIPCHK(launch_sssp_batch(K, dev_csr(top), ws, top->d_bsrc.p,
-                                         top->d_srcsh.p, top->d_h0seed.p, (int)rows,
-                                         measured ? K : kf, top->d_targets.p,
-                                         (int)A, delta, bp, top->iterGuard, out_lr, out_hops,
-                                         out_rowmin, top->d_stats.p, st));
-                HIPCHK(hipEventRecord(top->ev1, st));
-                HIPCHK(hipStreamSynchronize(st));  // the kernel's wall time goes to step 3
-                bstep_mark(top, 3);
-                if (ws.btrace) {  // read back after the build's closing event (below)
-                    bt.kf = measured ? 0 : kf;
-                    bt.slots = ws.slots;
-                    bt.start.swap(lstart);
-                    bt.file = btf;
-                }
-            }
-        }
-        HIPCHK(hipEventRecord(top->ev1, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (top->tpPending) {  // the asynchronous target preparation: iterations until the fixpoint
-            top->tpPending = false;
-            const int nit = std::max(0, top->targetKappa);
-            std::vector<unsigned int> ch((size_t)nit + 1);
-            HIPCHK(hipMemcpy(ch.data(), top->d_kfChanged.p, sizeof(unsigned int) * ch.size(),
-                             hipMemcpyDeviceToHost));
-            int it = 0;
-            while (it < nit && ch[(size_t)it + 1]) it++;  // the first iteration that changed nothing
-            top->stats.target_kappa_iters = it;
-            float ms = 0.0f;
-            HIPCHK(hipEventElapsedTime(&ms, top->evp0, top->evp1));
-            top->stats.target_prep_ms = ms;  // its GPU time (overlapped with the source order)
-        }
-        // the batch times: the sources' costs (option balance) and the SHD_BATCH_TRACE file -- after
-        // ev1, so the copy and the host work stay out of the kernel's event time
-        if (!bt.start.empty()) {
-            const int64_t lnbat = (int64_t)bt.start.size() - 1;
-            const std::vector<uint32_t>& psrc = top->layPsrc;
-            std::vector<unsigned long long> bv((size_t)lnbat * kBTraceWords);
-            HIPCHK(hipMemcpy(bv.data(), top->d_btrace.p, 8 * kBTraceWords * (size_t)lnbat, hipMemcpyDeviceToHost));
-            if (top->balance) record_costs(top, psrc, bt.start, bv);
-            if (bt.file && *bt.file) {
-                if (FILE* f = fopen(bt.file, "ab")) {
-                    const int64_t hdr[4] = {lnbat, (int64_t)bt.kf, (int64_t)bt.slots, rows};
-                    fwrite(hdr, 8, 4, f);
-                    fwrite(bv.data(), 8, bv.size(), f);
-                    for (int64_t i = 0; i < rows; i++) {
-                        const double p = top->hp->pot[(size_t)psrc[(size_t)i]];
-                        const int64_t rec[2] = {(int64_t)psrc[(size_t)i], 0};
-                        fwrite(rec, 8, 1, f);
-                        fwrite(&p, 8, 1, f);
-                    }
-                    fclose(f);
-                }
-            }
-        }
-        // rows that need igraph's heap pop order: replayed exactly on the GPU
-        std::vector<uint32_t> rlist;
-        top->stats.tie_dense = dense || probeDense ? 1 : 0;
-        if (allReplay || probeDense) {
-            rlist.resize((size_t)rows);
-            std::iota(rlist.begin(), rlist.end(), 0u);
-        } else if (top->tieReplay) {
-            std::vector<uint8_t> fl((size_t)rows);
-            HIPCHK(hipMemcpy(fl.data(), top->d_rowflag.p, (size_t)rows, hipMemcpyDeviceToHost));
-            for (int64_t i = 0; i < rows; i++)
-                if (fl[(size_t)i]) rlist.push_back((uint32_t)i);
-            if (rows >= 64 && (int64_t)rlist.size() * 10 >= rows * 9) top->tieDense = true;
-        }
-        top->replayPending = false;
-        // builds that run only the replay (tie-dense, directed, multigraph, replay_all): the
-        // batch workspace (~110 GB at C4) goes back so the replay can hold more rows at once
-        if (allReplay || probeDense) release_workspace(top);
-        if (!rlist.empty()) {
-            r = upload_replay(top);
-            if (r) return r;
-            r = ensure_replay_ws(top, (int)rlist.size());
-            if (r) return r;
-            r = upload_target_bits(top, tgt, st);
-            if (r) return r;
-            HIPCHK(top->d_rrows.ensure(rlist.size()));
-            HIPCHK(hipMemcpy(top->d_rrows.p, rlist.data(), 4 * rlist.size(), hipMemcpyHostToDevice));
-            HIPCHK(hipEventRecord(top->evr0, st));
-            HIPCHK(launch_heap_replay(replay_csr(top), replay_ws(top), top->d_sources.p,
-                                      top->d_rrows.p, (int)rlist.size(), top->d_targets.p, (int)A,
-                                      0, out_lr, out_hops, out_rowmin, top->d_stats.p, nullptr,
-                                      nullptr, st));
-            HIPCHK(hipEventRecord(top->evr1, st));
-            HIPCHK(hipStreamSynchronize(st));
-            top->replayPending = true;
-        }
-    }
-    top->rowsPending = true;
-    top->stats.batch = top->isComplete ? 0 : batch_k(top);
-    top->stats.sources = rows;
-    top->stats.targets = A;
-    return 0;
-}
-
-int collect_row_stats(Topology* top) {
-    if (!top->rowsPending) return 0;
-    HIPCHK(hipEventSynchronize(top->ev1));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, top->ev0, top->ev1));
-    unsigned long long h[ST_COUNT];
-    HIPCHK(hipMemcpy(h, top->d_stats.p, sizeof h, hipMemcpyDeviceToHost));
-    top->stats.sssp_kernel_ms = ms;
-    top->stats.build_ms = ms;
-    top->stats.replay_ms = 0.0;
-    if (top->replayPending) {
-        float rms = 0;
-        HIPCHK(hipEventSynchronize(top->evr1));
-        HIPCHK(hipEventElapsedTime(&rms, top->evr0, top->evr1));
-        top->stats.replay_ms = rms;
-        top->stats.build_ms += rms;
-        top->replayPending = false;
-    }
-    top->stats.ambiguous_pairs = (int64_t)h[ST_AMBIGUOUS];
-    top->stats.relaxations = (int64_t)h[ST_RELAX];
-    top->stats.long_paths = (int64_t)h[ST_LONGPATH];
-    top->stats.errors = (int64_t)h[ST_ERRORS];
-    {
-        int khz = 0;
-        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, top->devId) != hipSuccess || khz <= 0)
-            khz = 100000;
-        for (int i = 0; i < 4; i++) top->stats.phase_ms[i] = (double)h[ST_T_INIT + i] / (double)khz;
-        for (int i = 0; i < 4; i++) top->stats.parent_phase_ms[i] = (double)h[ST_PT0 + i] / (double)khz;
-    }
-    top->stats.near_iterations = (int64_t)h[ST_NEAR_IT];
-    top->stats.far_splits = (int64_t)h[ST_SPLITS];
-    for (int i = 0; i < 8; i++) top->stats.events[i] = (int64_t)h[ST_EV0 + i];
-    top->stats.slots = top->isComplete ? 0 : (top->slotsUsed > 0 ? top->slotsUsed : top->slots);
-    double gm;
-    memcpy(&gm, &h[ST_GLOBAL_MIN], sizeof gm);
-    top->eagerMin = std::isinf(gm) ? -1.0 : gm;
-    if (h[ST_OVERSITE]) WARNING("queue overflow sites 0x%llx", h[ST_OVERSITE]);
-    if (h[ST_FARSCAN])
-        MESSAGE("%llu sources overflowed the far pile and finished with scanning splits",
-                h[ST_FARSCAN]);
-    top->stats.far_scan_sources = (int64_t)h[ST_FARSCAN];
-    top->stats.replay_rows = (int64_t)h[ST_RP_ROWS];
-    top->stats.touched_lines = (int64_t)h[ST_TOUCHED];
-    top->stats.walk_steps = (int64_t)h[ST_WALK];
-    top->stats.batches = top->lastBatches;
-    for (int i = 0; i < 4; i++) top->stats.walk_kinds[i] = (int64_t)h[ST_WK0 + i];
-    top->stats.replay_pops = (int64_t)h[ST_RP_POPS];
-    top->stats.replay_pushes = (int64_t)h[ST_RP_PUSH];
-    top->stats.replay_modifies = (int64_t)h[ST_RP_MOD];
-    for (int i = 0; i < 6; i++) top->stats.replay_lines[i] = (int64_t)h[ST_RP_L0 + i];
-    {
-        int khz = 0;
-        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, top->devId) != hipSuccess || khz <= 0)
-            khz = 100000;
-        for (int i = 0; i < 4; i++) top->stats.replay_phase_ms[i] = (double)h[ST_RP_T0 + i] / (double)khz;
-        top->stats.replay_sink_rounds = (int64_t)h[ST_RP_T0 + 4];
-        top->stats.replay_heap_sum = (int64_t)h[ST_RP_T0 + 5];
-        for (int i = 0; i < 3; i++) top->stats.replay_sink_ms[i] = (double)h[ST_RP_T0 + 6 + i] / (double)khz;
-        top->stats.replay_pf_hits = (int64_t)h[ST_RP_T0 + 9];
-        top->stats.replay_skips = (int64_t)h[ST_RP_SKIP];
-        for (int i = 0; i < 6; i++) top->stats.batch_wave_ms[i] = (double)h[ST_BT0 + i] / (double)khz;
-        top->stats.batch_rounds = (int64_t)h[ST_BT0 + 6];
-        top->stats.batch_edges_b = (int64_t)h[ST_BT0 + 7];
-        for (int i = 0; i < 4; i++) top->stats.sweep_events[i] = (int64_t)h[ST_SW0 + i];
-        for (int i = 0; i < 16; i++) top->stats.write_lines[i] = (int64_t)h[ST_WL0 + i];
-        for (int i = 0; i < 8; i++) top->stats.read_lines[i] = (int64_t)h[ST_RL0 + i];
-    }
-    top->stats.replay_slots = top->stats.replay_rows ? std::min(top->rslots, top->rslotsUse) : 0;
-    top->stats.replay_int_keys = top->stats.replay_rows && top->replayIntOpt && top->replayIntOk ? 1 : 0;
-    {
-        int khz = 0;
-        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, top->devId) != hipSuccess || khz <= 0)
-            khz = 100000;
-        top->stats.split_ms = (double)h[ST_T_SPLIT] / (double)khz;
-    }
-    if (h[ST_OVERFLOW]) CRITICAL("SSSP queue overflow / iteration guard (code %llu)", h[ST_OVERFLOW]);
-    if (top->stats.ambiguous_pairs && !top->tieReplay)
-        WARNING("%lld pairs cross a parent tie (equal d[u]): igraph's heap pop order decides them "
-                "in the reference; tie_replay is off, so the lowest adjacency slot is used here",
-                (long long)top->stats.ambiguous_pairs);
-    top->rowsPending = false;
-    return h[ST_OVERFLOW] ? -4 : 0;
-}
-
 void push_min_to_engine(double m) {
     if (worker_updateMinTimeJump && m > 0) worker_updateMinTimeJump(m);
 }
@@ -1901,436 +1076,9 @@ bool table_current(Topology* top) {
            top->tableGen.load(std::memory_order_acquire) == top->setGen.load();
 }
 
-// ---------------------------------------------------------------------------------------------
-// multi-GPU build inside one process: no Python, no torch.distributed
-// ---------------------------------------------------------------------------------------------
-// RCCL is loaded on first use (dlopen by soname: a process that already holds RCCL, e.g. through
-// torch, shares that copy; a single-GPU user never needs it).
-struct RcclApi {
-    bool ok = false;
-    std::string why;
-    ncclResult_t (*commInitAll)(ncclComm_t*, int, const int*) = nullptr;
-    ncclResult_t (*commDestroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*allGather)(const void*, void*, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*allReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t,
-                              hipStream_t) = nullptr;
-    ncclResult_t (*groupStart)() = nullptr;
-    ncclResult_t (*groupEnd)() = nullptr;
-    const char* (*errStr)(ncclResult_t) = nullptr;
-};
-
-RcclApi& rccl() {
-    static RcclApi api;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        void* h = nullptr;
-        for (const char* n : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"})
-            if ((h = dlopen(n, RTLD_NOW | RTLD_GLOBAL))) break;
-        if (!h) {
-            api.why = dlerror() ? dlerror() : "librccl.so.1 not found";
-            return;
-        }
-        auto sym = [&](const char* n) { return dlsym(h, n); };
-        api.commInitAll = (decltype(api.commInitAll))sym("ncclCommInitAll");
-        api.commDestroy = (decltype(api.commDestroy))sym("ncclCommDestroy");
-        api.allGather = (decltype(api.allGather))sym("ncclAllGather");
-        api.allReduce = (decltype(api.allReduce))sym("ncclAllReduce");
-        api.groupStart = (decltype(api.groupStart))sym("ncclGroupStart");
-        api.groupEnd = (decltype(api.groupEnd))sym("ncclGroupEnd");
-        api.errStr = (decltype(api.errStr))sym("ncclGetErrorString");
-        api.ok = api.commInitAll && api.commDestroy && api.allGather && api.allReduce &&
-                 api.groupStart && api.groupEnd && api.errStr;
-        if (!api.ok) api.why = "RCCL symbols missing";
-    });
-    return api;
-}
-
-#define NCCLCHK(expr)                                                                        \
-    do {                                                                                     \
-        ncclResult_t _r = (expr);                                                            \
-        if (_r != ncclSuccess) {                                                             \
-            CRITICAL("RCCL error %s at %s:%d (%s)", rccl().errStr(_r), __FILE__, __LINE__, #expr); \
-            return -200 - (int)_r;                                                           \
-        }                                                                                    \
-    } while (0)
-
-int num_devices() {
-    int n = 0;
-    return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
-}
-
 // The engine of device slot d: slot 0 is the Topology itself, the others are peers holding the
 // same graph and columns on their own device (stream, CSR copy, workspaces, table).
 Topology* slot_engine(Topology* top, int d) { return d == 0 ? top : top->peers[(size_t)d - 1]; }
-
-Topology* make_peer(Topology* top, int phys) {
-    Topology* p = new Topology(top->gp);
-    p->isComplete = top->isComplete;
-    p->isDirected = top->isDirected;
-    p->hasMultiEdges = top->hasMultiEdges;
-    p->abortOnError = top->abortOnError.load();
-    p->lazy = false;
-    p->device = phys;
-    p->isPeer = true;
-    return p;
-}
-
-// options and columns of the owner, copied before every multi-device build
-void sync_peer(Topology* top, Topology* p) {
-    p->delta = top->delta;
-    p->slotsOpt = top->slotsOpt;
-    p->hubLimit = top->hubLimit;
-    p->parHubs = top->parHubs;
-    p->rsChunk = top->rsChunk;
-    p->batchK = top->batchK;
-    p->iterGuard = top->iterGuard;
-    p->tieReplay = top->tieReplay;
-    p->replayAll = top->replayAll;
-    p->tieDenseOpt = top->tieDenseOpt;
-    p->tieDense = p->tieDense || top->tieDense;
-    p->replaySlotsOpt = top->replaySlotsOpt;
-    p->replayLandmark = top->replayLandmark;
-    p->replayIntOpt = top->replayIntOpt;
-    if (top->meanLat >= 0 && !(p->meanLat >= 0)) {  // the owner's edge scan (same graph)
-        p->minLat = top->minLat;
-        p->meanLat = top->meanLat;
-        p->replayIntOk = top->replayIntOk;
-    }
-    p->sourceOrder = top->sourceOrder;
-    p->balance = top->balance;
-    p->batchOrder = top->batchOrder;
-    p->batchFill = top->batchFill;
-    p->h0Phase = top->h0Phase;
-    p->h0PhaseSet = top->h0PhaseSet;
-    p->targetSkip = top->targetSkip;
-    p->targetKappa = top->targetKappa;
-    p->targetResort = top->targetResort;
-    p->leafTargets = top->leafTargets;
-    if (p->h0Seed != top->h0Seed) {
-        p->h0Seed = top->h0Seed;
-        p->ordUploaded = false;
-    }
-    p->attached = top->attached;
-    p->colOf = top->colOf;
-    p->A = top->A;
-    p->geomInit = true;
-}
-
-template <class T>
-hipError_t peer_copy(DevBuf<T>& dst, int ddev, const DevBuf<T>& src, int sdev, hipStream_t st) {
-    if (!src.p || src.n == 0) return hipSuccess;
-    const hipError_t e = dst.ensure(src.n);
-    if (e != hipSuccess) return e;
-    return hipMemcpyPeerAsync(dst.p, ddev, src.p, sdev, sizeof(T) * src.n, st);
-}
-
-// A peer engine takes the owner's prepared graph: the device CSR and landmark arrays are copied
-// device to device (xGMI peer copies; the same device for a test configuration) and the host side
-// is shared -- the graph is prepared once per multi-GPU build, not once per device.
-int copy_csr_from(Topology* p, int pdev, Topology* o, int odev) {
-    hipStream_t st = p->stream;
-    if (pdev != odev) {
-        const hipError_t e = hipDeviceEnablePeerAccess(odev, 0);
-        if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled)
-            (void)hipGetLastError();  // no direct access: the copies are staged by the runtime
-    }
-    HIPCHK(peer_copy(p->d_rowptr, pdev, o->d_rowptr, odev, st));
-    HIPCHK(peer_copy(p->d_adj, pdev, o->d_adj, odev, st));
-    HIPCHK(peer_copy(p->d_adjo, pdev, o->d_adjo, odev, st));
-    HIPCHK(peer_copy(p->d_rowptrIn, pdev, o->d_rowptrIn, odev, st));
-    HIPCHK(peer_copy(p->d_adjk, pdev, o->d_adjk, odev, st));
-    HIPCHK(peer_copy(p->d_kap, pdev, o->d_kap, odev, st));
-    HIPCHK(peer_copy(p->d_ksum, pdev, o->d_ksum, odev, st));
-    HIPCHK(peer_copy(p->d_kap0, pdev, o->d_kap0, odev, st));
-    HIPCHK(peer_copy(p->d_spt, pdev, o->d_spt, odev, st));
-    HIPCHK(peer_copy(p->d_sptPar, pdev, o->d_sptPar, odev, st));
-    HIPCHK(peer_copy(p->d_pot, pdev, o->d_pot, odev, st));
-    HIPCHK(peer_copy(p->d_aloss, pdev, o->d_aloss, odev, st));
-    HIPCHK(peer_copy(p->d_vloss, pdev, o->d_vloss, odev, st));
-    HIPCHK(peer_copy(p->d_selfLat, pdev, o->d_selfLat, odev, st));
-    HIPCHK(peer_copy(p->d_selfLoss, pdev, o->d_selfLoss, odev, st));
-    HIPCHK(peer_copy(p->d_eu, pdev, o->d_eu, odev, st));
-    HIPCHK(peer_copy(p->d_ev, pdev, o->d_ev, odev, st));
-    HIPCHK(peer_copy(p->d_elat, pdev, o->d_elat, odev, st));
-    HIPCHK(peer_copy(p->d_eloss, pdev, o->d_eloss, odev, st));
-    HIPCHK(peer_copy(p->d_inv, pdev, o->d_inv, odev, st));
-    HIPCHK(peer_copy(p->d_hseg, pdev, o->d_hseg, odev, st));
-    HIPCHK(peer_copy(p->d_hmulti, pdev, o->d_hmulti, odev, st));
-    p->hsegRows = o->hsegRows;
-    p->hsegN = o->hsegN;
-    p->hmultiN = o->hmultiN;
-    HIPCHK(hipStreamSynchronize(st));
-    p->hp = o->hp;
-    p->rowsSorted = o->rowsSorted;
-    p->adjkPlain = o->adjkPlain;
-    p->adjkFlagged = o->adjkFlagged;
-    p->adjkResorted = o->adjkResorted;
-    p->adjkLeaf = o->adjkLeaf;
-    p->adjkTargets = o->adjkTargets;
-    p->csrUploaded = true;
-    return 0;
-}
-
-// N devices: slot d builds rows [d*R, min(A, (d+1)*R)) into its own full-size buffers (R*N rows,
-// padded), then the rows are exchanged so that every device holds the whole table:
-// ncclAllGather (in place) of the {lat, rel} rows, the u16 hop rows and the row minima, and
-// ncclAllReduce(MIN) of the per-device minimum (u64 bits of a non-negative f64 order like the
-// values) -> topology_getMinimumLatency / the runahead (shd-master.c:113-124).  Several slots on
-// one physical device (a test configuration: RCCL refuses duplicate devices) exchange with
-// device copies instead.
-int build_multi(Topology* top) {
-    const int N = std::max(1, top->devicesOpt);
-    const int ndev = num_devices();
-    if (ndev <= 0) {
-        CRITICAL("no HIP device available: the routing engine runs on the GPU only");
-        return -1;
-    }
-    while ((int)top->peers.size() < N - 1)
-        top->peers.push_back(make_peer(top, (top->device + (int)top->peers.size() + 1) % ndev));
-    for (int d = 1; d < N; d++) sync_peer(top, slot_engine(top, d));
-    const int64_t A = top->A;
-    const int64_t R = (A + N - 1) / N;
-    top->shardRows = R;
-    std::vector<int> phys(N);
-    bool distinct = true;
-    for (int d = 0; d < N; d++) {
-        phys[(size_t)d] = slot_engine(top, d)->device % ndev;
-        for (int e = 0; e < d; e++) distinct = distinct && phys[(size_t)e] != phys[(size_t)d];
-    }
-    for (int d = 0; d < N; d++) {
-        int k = 0;
-        for (int e = 0; e < N; e++) k += phys[(size_t)e] == phys[(size_t)d];
-        slot_engine(top, d)->memShareDiv = k;
-    }
-    // 0) the graph is prepared once, on this engine's device, and copied to the peers
-    {
-        const auto tp = std::chrono::steady_clock::now();
-        HIPCHK(hipSetDevice(phys[0]));
-        int r = dev_init(top);
-        if (r) return r;
-        bool did = false;
-        if (!top->isComplete) {
-            did = !top->csrUploaded;
-            r = upload_csr(top);
-            if (r) return r;
-            (void)default_delta(top);  // the mean latency, once (peers copy it)
-        }
-        // the peers in parallel: a device's first stream costs ~80 ms of HIP queue setup
-        std::vector<int> prc((size_t)N, 0);
-        std::vector<uint8_t> pdid((size_t)N, 0);
-        std::vector<std::thread> pth;
-        for (int d = 1; d < N; d++)
-            pth.emplace_back([&, d]() {
-                auto one = [&]() -> int {
-                    Topology* T = slot_engine(top, d);
-                    reset_build_stats(T);
-                    HIPCHK(hipSetDevice(phys[(size_t)d]));
-                    int rr = dev_init(T);
-                    if (rr) return rr;
-                    T->minLat = top->minLat;
-                    T->meanLat = top->meanLat;
-                    T->replayIntOk = top->replayIntOk;  // the owner's edge scan (same graph)
-                    if (!top->isComplete && !T->csrUploaded) {
-                        rr = copy_csr_from(T, phys[(size_t)d], top, phys[0]);
-                        if (rr) return rr;
-                        pdid[(size_t)d] = 1;
-                    }
-                    return 0;
-                };
-                prc[(size_t)d] = one();
-            });
-        for (auto& x : pth) x.join();
-        for (int d = 1; d < N; d++) {
-            if (prc[(size_t)d]) return prc[(size_t)d];
-            did = did || pdid[(size_t)d];
-        }
-        HIPCHK(hipSetDevice(phys[0]));
-        if (did)  // preparation + the peers' copies
-            top->stats.csr_ms = std::chrono::duration<double, std::milli>(
-                std::chrono::steady_clock::now() - tp).count();
-    }
-    // 1) rows: device d builds rows [d R, (d+1) R) in its own host thread.
-    // 2) exchange, option "exchange" (VERDICT r05 item 3):
-    //    * push (2; the default for engines sharing a device): each device, as soon as its own rows
-    //      are done, copies them into every other device's table on its exchange stream (peer DMA
-    //      over xGMI) while the slower devices still compute -- only the last shard's copies are
-    //      exposed;
-    //    * rccl (1; the default for distinct devices): ncclAllGather of the rows, hops and row
-    //      minima in place once every shard is done (the north-star exchange).
-    //    The minimum (MIN over u64 bits of a non-negative f64 orders like the values) goes to
-    //    every device -> topology_getMinimumLatency / the runahead (shd-master.c:113-124): an
-    //    ncclAllReduce with RCCL, from the host's per-device minima with push.
-    bool useRccl = distinct && top->xchgMode != 2;
-    if (useRccl) {
-        RcclApi& api = rccl();
-        if (!api.ok) {
-            WARNING("RCCL unavailable (%s): the rows are exchanged by peer copies", api.why.c_str());
-            useRccl = false;
-        } else if (top->commDevs != phys) {
-            for (ncclComm_t c : top->comms) (void)api.commDestroy(c);
-            top->comms.assign((size_t)N, nullptr);
-            top->commDevs.clear();
-            const ncclResult_t e = api.commInitAll(top->comms.data(), N, phys.data());
-            if (e != ncclSuccess) {
-                WARNING("ncclCommInitAll failed (%s): the rows are exchanged by peer copies",
-                        api.errStr(e));
-                top->comms.clear();
-                useRccl = false;
-            } else {
-                top->commDevs = phys;
-            }
-        }
-    }
-    const bool push = !useRccl;
-    // every engine's table buffers first: a device's push may arrive before the peer's own rows
-    for (int d = 0; d < N; d++) {
-        Topology* T = slot_engine(top, d);
-        HIPCHK(hipSetDevice(phys[(size_t)d]));
-        HIPCHK(T->d_lr.ensure((size_t)(R * N * A)));
-        HIPCHK(T->d_hops.ensure((size_t)(R * N * A)));
-        HIPCHK(T->d_rowmin.ensure((size_t)(R * N)));
-        if (push && !T->xstream) HIPCHK(hipStreamCreateWithFlags(&T->xstream, hipStreamNonBlocking));
-        if (push && distinct)
-            for (int e = 0; e < N; e++) {
-                if (e == d) continue;
-                const hipError_t pe = hipDeviceEnablePeerAccess(phys[(size_t)e], 0);
-                if (pe != hipSuccess && pe != hipErrorPeerAccessAlreadyEnabled)
-                    (void)hipGetLastError();  // no direct access: the runtime stages the copies
-            }
-    }
-    using clk = std::chrono::steady_clock;
-    std::vector<int> rc(N, 0);
-    std::vector<double> dwall((size_t)N, 0.0);
-    std::vector<unsigned long long> dmin((size_t)N, 0x7FF0000000000000ull);
-    std::vector<int64_t> drows((size_t)N, 0);
-    std::vector<clk::time_point> tdone((size_t)N), tpushed((size_t)N);
-    const auto tb = clk::now();
-    std::vector<std::thread> th;
-    for (int d = 0; d < N; d++)
-        th.emplace_back([&, d]() {
-            Topology* T = slot_engine(top, d);
-            auto run = [&]() -> int {
-                HIPCHK(hipSetDevice(phys[(size_t)d]));
-                int r = dev_init(T);
-                if (r) return r;
-                HIPCHK(hipSetDevice(phys[(size_t)d]));
-                const int64_t r0 = std::min(A, d * R), r1 = std::min(A, r0 + R);
-                if (r1 > r0) {
-                    r = enqueue_rows(T, r0, r1, T->d_lr.p + r0 * A, T->d_hops.p + r0 * A,
-                                     T->d_rowmin.p + r0, T->stream);
-                    if (r) return r;
-                    r = collect_row_stats(T);
-                    if (r) return r;
-                    HIPCHK(hipMemcpy(&dmin[(size_t)d], T->d_stats.p + ST_GLOBAL_MIN, 8, hipMemcpyDeviceToHost));
-                }
-                drows[(size_t)d] = r1 - r0;
-                tdone[(size_t)d] = clk::now();
-                if (push && r1 > r0) {  // this shard into every other device's table, now
-                    for (int e = 0; e < N; e++) {
-                        if (e == d) continue;
-                        Topology* S = slot_engine(top, e);
-                        const int pd = phys[(size_t)e], ps = phys[(size_t)d];
-                        const size_t n = (size_t)((r1 - r0) * A);
-                        HIPCHK(hipMemcpyPeerAsync(S->d_lr.p + r0 * A, pd, T->d_lr.p + r0 * A, ps, sizeof(double2) * n, T->xstream));
-                        HIPCHK(hipMemcpyPeerAsync(S->d_hops.p + r0 * A, pd, T->d_hops.p + r0 * A, ps, 2 * n, T->xstream));
-                        HIPCHK(hipMemcpyPeerAsync(S->d_rowmin.p + r0, pd, T->d_rowmin.p + r0, ps, 8 * (size_t)(r1 - r0), T->xstream));
-                    }
-                    HIPCHK(hipStreamSynchronize(T->xstream));
-                }
-                tpushed[(size_t)d] = clk::now();
-                return 0;
-            };
-            rc[(size_t)d] = run();
-            dwall[(size_t)d] = std::chrono::duration<double, std::milli>(clk::now() - tb).count();
-        });
-    for (auto& x : th) x.join();
-    for (int d = 0; d < N; d++)
-        if (rc[(size_t)d]) return rc[(size_t)d];
-    auto tfirst = tdone[0], tlast = tdone[0];
-    for (int d = 1; d < N; d++) {
-        tfirst = std::min(tfirst, tdone[(size_t)d]);
-        tlast = std::max(tlast, tdone[(size_t)d]);
-    }
-    top->stats.exchange_kind = N > 1 || top->forceRccl ? (useRccl ? 1 : 2) : 0;
-    top->stats.exchange_bytes = (int64_t)(N - 1) * R * (A * (int64_t)(sizeof(double2) + 2) + 8);
-    if (useRccl) {
-        RcclApi& api = rccl();
-        NCCLCHK(api.groupStart());
-        for (int d = 0; d < N; d++) {
-            Topology* T = slot_engine(top, d);
-            ncclComm_t c = top->comms[(size_t)d];
-            const size_t lrB = (size_t)(R * A) * sizeof(double2), hB = (size_t)(R * A) * 2;
-            NCCLCHK(api.allGather((const char*)T->d_lr.p + (size_t)d * lrB, T->d_lr.p, lrB, ncclUint8, c, T->stream));
-            NCCLCHK(api.allGather((const char*)T->d_hops.p + (size_t)d * hB, T->d_hops.p, hB, ncclUint8, c, T->stream));
-            NCCLCHK(api.allGather(T->d_rowmin.p + (size_t)d * (size_t)R, T->d_rowmin.p, (size_t)R, ncclFloat64, c, T->stream));
-        }
-        NCCLCHK(api.groupEnd());
-        for (int d = 0; d < N; d++) {
-            Topology* T = slot_engine(top, d);
-            HIPCHK(hipSetDevice(phys[(size_t)d]));
-            HIPCHK(hipMemcpyAsync(T->d_stats.p + ST_GLOBAL_MIN, &dmin[(size_t)d], 8, hipMemcpyHostToDevice, T->stream));
-        }
-        NCCLCHK(api.groupStart());
-        for (int d = 0; d < N; d++) {
-            Topology* T = slot_engine(top, d);
-            NCCLCHK(api.allReduce(T->d_stats.p + ST_GLOBAL_MIN, T->d_stats.p + ST_GLOBAL_MIN, 1, ncclUint64, ncclMin, top->comms[(size_t)d], T->stream));
-        }
-        NCCLCHK(api.groupEnd());
-        for (int d = 0; d < N; d++) {
-            HIPCHK(hipSetDevice(phys[(size_t)d]));
-            HIPCHK(hipStreamSynchronize(slot_engine(top, d)->stream));
-        }
-    } else {
-        unsigned long long gmin = 0x7FF0000000000000ull;
-        for (int d = 0; d < N; d++) gmin = std::min(gmin, dmin[(size_t)d]);
-        for (int d = 0; d < N; d++) {
-            Topology* T = slot_engine(top, d);
-            HIPCHK(hipSetDevice(phys[(size_t)d]));
-            HIPCHK(hipMemcpy(T->d_stats.p + ST_GLOBAL_MIN, &gmin, 8, hipMemcpyHostToDevice));
-        }
-    }
-    HIPCHK(hipSetDevice(phys[0]));
-    auto tend = clk::now();
-    if (push)
-        for (int d = 0; d < N; d++) tend = std::max(tend, tpushed[(size_t)d]);
-    const auto tx0 = useRccl ? tlast : tfirst;
-    top->stats.exchange_ms = std::chrono::duration<double, std::milli>(tend - tx0).count();
-    top->stats.exchange_exposed_ms = std::chrono::duration<double, std::milli>(tend - tlast).count();
-    unsigned long long gm = 0;
-    HIPCHK(hipMemcpy(&gm, top->d_stats.p + ST_GLOBAL_MIN, 8, hipMemcpyDeviceToHost));
-    double g;
-    memcpy(&g, &gm, 8);
-    top->eagerMin = std::isinf(g) ? -1.0 : g;
-    // whole-job statistics: the slowest device's kernels, every device's counts
-    for (int d = 0; d < 8; d++) {
-        top->stats.device_kernel_ms[d] = top->stats.device_build_ms[d] = 0.0;
-        top->stats.device_rows[d] = 0;
-    }
-    for (int d = 0; d < std::min(N, 8); d++) {
-        top->stats.device_kernel_ms[d] = drows[(size_t)d] > 0 ? slot_engine(top, d)->stats.build_ms : 0.0;
-        top->stats.device_build_ms[d] = dwall[(size_t)d];
-        top->stats.device_rows[d] = drows[(size_t)d];
-    }
-    top->stats.devices = N;
-    top->stats.sources = A;
-    for (int d = 1; d < N; d++) {
-        const ShdStats& o = slot_engine(top, d)->stats;
-        top->stats.sssp_kernel_ms = std::max(top->stats.sssp_kernel_ms, o.sssp_kernel_ms);
-        top->stats.target_prep_ms = std::max(top->stats.target_prep_ms, o.target_prep_ms);
-        top->stats.order_ms = std::max(top->stats.order_ms, o.order_ms);
-        top->stats.replay_prep_ms = std::max(top->stats.replay_prep_ms, o.replay_prep_ms);
-        top->stats.touched_lines += o.touched_lines;
-        top->stats.replay_ms = std::max(top->stats.replay_ms, o.replay_ms);
-        top->stats.build_ms = std::max(top->stats.build_ms, o.build_ms);
-        top->stats.ambiguous_pairs += o.ambiguous_pairs;
-        top->stats.replay_rows += o.replay_rows;
-        top->stats.replay_skips += o.replay_skips;
-        top->tieDense = top->tieDense || slot_engine(top, d)->tieDense;
-        top->stats.errors += o.errors;
-        top->stats.relaxations += o.relaxations;
-    }
-    return 0;
-}
 
 // whole-table build on this GPU (for the current attached set)
 int ensure_table(Topology* top) {
@@ -2979,9 +1727,7 @@ void topology_free(Topology* top) {
     for (Topology* p : top->peers) topology_free(p);
     top->peers.clear();
     monitors_release(top);
-    if (!top->comms.empty() && rccl().ok)
-        for (ncclComm_t c : top->comms) (void)rccl().commDestroy(c);
-    top->comms.clear();
+    release_comms(top);
     if (top->devInit) {
         (void)hipStreamSynchronize(top->stream);
         (void)hipEventDestroy(top->ev0);

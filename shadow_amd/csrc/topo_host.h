@@ -1,6 +1,7 @@
-// topo_host.h -- what the host units of libshdtopo (topo_core.cpp, topo_flows.cpp,
-// topo_monitor_host.cpp) share: logging, DevBuf, struct _Topology, the core functions the flow
-// analysis calls and the flow analysis' own shared parts.  Included by the .cpp units only.
+// topo_host.h -- what the host units of libshdtopo (topo_core.cpp, topo_build.cpp, topo_flows.cpp,
+// topo_monitor_host.cpp) share: logging, DevBuf, struct _Topology, the core functions the table
+// build and the flow analysis call and the flow analysis' own shared parts.  Included by the
+// .cpp units only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -480,11 +481,38 @@ struct _Topology {
 
 namespace shdtopo {
 
-// ---- topo_core.cpp: what the flow analysis calls (each holds buildMu) ----
+// Hubs of the tail grouping: the tail is grouped by its highest-ranked neighbour
+// among the first kGroupHubs vertices of the degree order (the count the former single-source
+// kernel held in LDS, where the grouping was tuned).
+constexpr int64_t kGroupHubs = 16565;
+
+// ---- topo_build.cpp: the whole-table build (each holds buildMu) ----
+int enqueue_rows(Topology* top, int64_t row0, int64_t row1, double2* out_lr, uint16_t* out_hops,
+                 double* out_rowmin, hipStream_t st);
+int collect_row_stats(Topology* top);
+int build_multi(Topology* top);
+int num_devices();
+void bstep_mark(Topology* top, int i);
+void reset_build_stats(Topology* top);
+void plan_long_rows(const uint32_t* rowptr, int64_t V, std::vector<uint32_t>& pos,
+                    std::vector<uint32_t>& row, int* end_bit);
+int ensure_kprime_scratch(Topology* top, KprimeScratch* out);
+// (file-local before the split: hidden, so the library exports what it did)
+__attribute__((visibility("hidden"))) bool layout_from_costs(
+    const std::vector<double>& c, double a, int kf, int slots, int K, std::vector<uint32_t>& order,
+    std::vector<uint32_t>& lstart);
+__attribute__((visibility("hidden"))) void release_comms(Topology* top);
+
+// ---- topo_core.cpp: what the table build and the flow analysis call (each holds buildMu) ----
 int dev_init(Topology* top);
 uint64_t compute_geometry(Topology* top);
 int32_t vertex_of_ip(Topology* top, uint32_t ip);
-int collect_row_stats(Topology* top);
+void edge_scan(Topology* top);
+Topology* slot_engine(Topology* top, int d);
+HubSegs hub_segs(Topology* top);
+const uint32_t* adj_out(Topology* top);
+void release_workspace(Topology* top);
+double h0_phase(Topology* top, double delta);
 int upload_csr(Topology* top);
 int upload_replay(Topology* top);
 int ensure_replay_ws(Topology* top, int nrows);
