@@ -954,6 +954,102 @@ int64_t shdtopo_table_diff(Topology* a, Topology* b, ShdTableChange* out, int64_
                            double* rowWorstRise /* [A] */, int32_t* rowWorstCol /* [A] */);
 int shdtopo_table_diff_stats(Topology* a, ShdDiffStats* out);
 
+/* ---- flow impact: what a link failure does to a set of flows ----
+ * shdtopo_table_diff answers "which attached pairs change"; shdtopo_flow_impact answers it for
+ * traffic: n flows (source, destination, weight) are joined with the two device-resident tables of
+ * a and b on the device -- four random gathers per flow -- and only the changed flows, integer
+ * totals, a histogram of the delay rises and two per-column arrays leave it.
+ *
+ * Flows.  The host variant takes IPs and resolves them through a's map, as the trace and the load
+ * do (an end that is not on a vertex of the current attached set is unattached); weight NULL means
+ * 1 per flow.  The device variant takes the column arrays shdtopo_route_batch_device and
+ * shdtopo_monitor_feed_device take (a column outside [0, A) is unattached) and a u32 payload as
+ * the weight (NULL: 1 each); its kernels run on `stream` (NULL: a's own) behind whatever the
+ * caller enqueued there, and the call returns when they are done.  n <= 2^31 - 2.
+ *
+ * Comparison.  Flow i is compared when both ends are columns.  A compared flow is changed exactly
+ * when shdtopo_table_diff(a, b) would report its (srcCol, dstCol) pair: latency bits, reliability
+ * bits or hops differ; kind is that call's kind.  a's values are lat0 / rel0 / hops0, b's lat1 /
+ * rel1 / hops1.  Duplicate flows are separate flows.  Returns the number of changed flows; out
+ * receives the first min(total, cap) records in ascending flow order (cap = 0 with out = NULL
+ * sizes the buffer), nothing at or beyond cap is touched, and every other output is complete
+ * whatever cap is.  Any output pointer may be NULL.
+ *
+ * Sums.  Every sum is a u64 that wraps, so no output depends on flow order, tiling or scheduling;
+ * there is no floating-point sum.  delay = (uint64_t)ceil(lat * 1000000.0), the packet route's
+ * delay in ns, and a flow's rise or fall is the difference of its two delays.  The histogram
+ * covers the flows with kind & 1 by delay1 - delay0: a flow's bin is the number of edges <= its
+ * rise, so bin 0 holds the rises below riseEdgeNs[0], bin nb those at or above the last edge, and
+ * a rise equal to an edge goes to the upper bin; riseCount / riseWeight have nb + 1 entries,
+ * 0 <= nb <= 1024, nb = 0 gives one bin.  srcChangedWeight[c] / dstChangedWeight[c] (A entries)
+ * hold the weight of the changed flows that leave / enter column c.
+ *
+ * Errors, locks and side effects follow shdtopo_table_diff: -1 bad arguments (a NULL topology,
+ * n < 0 or too large, a NULL end array with n > 0, cap < 0, NULL out with cap > 0, nb outside
+ * [0, 1024], a NULL edge array with nb > 0, edges not strictly ascending); -4 the attached vertex
+ * lists differ; -6 the tables are on different devices; -5 the attached sets kept moving.
+ * Argument errors and -4 are returned before any device is used.  Missing tables are built as by
+ * shdtopo_build, then both build locks are taken, the lower address first.  The call materialises
+ * no lazy row, pushes no minimum and leaves ShdStats, the family's statistics and ShdDiffStats as
+ * they were; its timing events are its own.  a == b is valid and answered without a table: the
+ * flows are resolved (the device variant copies the columns and the payload to the host),
+ * compared, unattached and weight are filled, everything else is zero, worstFlow is -1 and the
+ * call returns 0.
+ *
+ * Device work (topo_impact.hip).  A count pass over tiles of 256 x U flows (tile_flows of the
+ * statistics) gathers {lat, rel} and hops from both tables, keeps one ballot word per 64 flows,
+ * reduces the totals in registers and LDS and numbers the tiles' changed flows; an exclusive scan
+ * places the tiles; a fill pass gathers again only for the words that have a changed flow below
+ * cap and writes the 48-B records at their ranks: flow order with no sort and no atomic.
+ * shdtopo_flow_impact_stats reads the statistics of the last call in which `a` was the first
+ * argument.  bytes_model, per flow: the count pass reads 8 B of columns and the weight (8 B, 4 B
+ * or none), and for a compared flow two 16-B records and two 2-B hops (36 B); it writes one 8-B
+ * word per 64 flows; the fill pass reads 8 B of columns and 36 B of table and writes 48 B for
+ * every record it writes. */
+typedef struct {            /* 48 B: three 16-B stores on the device */
+    int64_t  flow;          /* request index i */
+    double   lat0, lat1, rel0, rel1;
+    uint16_t hops0, hops1;
+    uint32_t kind;          /* shdtopo_table_diff's kind bits: 1 rose, 2 fell, 4 rel, 8 hops */
+} ShdFlowChange;
+
+typedef struct {
+    int64_t  flows, compared, unattached, changed;
+    uint64_t weight, changedWeight;          /* sums over compared / changed flows */
+    uint64_t kindCount[4], kindWeight[4];
+    uint64_t delayRiseNs, delayFallNs;       /* sum of w * |delay1 - delay0| over kind & 1 / kind & 2 */
+    uint64_t hopsRise, hopsFall;             /* sum of w * |hops1 - hops0| over hops1 > hops0 / hops1 < hops0 */
+    double   worstRise;                      /* max lat1 - lat0 (one f64 subtraction) over kind & 1; 0.0 if none */
+    int64_t  worstFlow;                      /* the lowest flow index reaching it; -1 if none */
+} ShdImpactTotals;
+
+typedef struct {
+    double  total_ms;       /* wall time of the call (table builds it had to wait for included) */
+    double  resolve_ms;     /* of it: resolving the IPs to columns on the host (device variant: 0) */
+    double  kernel_ms;      /* event time of count and scan, plus fill_ms */
+    double  fill_ms;        /* event time of the fill pass (0: no record was asked for) */
+    int64_t flows;          /* n */
+    int64_t changed;        /* the call's return value */
+    int64_t words_skipped;  /* 64-flow words (of (n + 63) / 64) the fill pass did not gather for */
+    int64_t bytes_model;    /* the per-flow byte model above, summed over the call */
+    int64_t tile_flows;     /* flows per workgroup of this build: 256 x U */
+} ShdImpactStats;
+
+int64_t shdtopo_flow_impact(Topology* a, Topology* b, const uint32_t* srcIP, const uint32_t* dstIP,
+                            const uint64_t* weight /* NULL: 1 each */, int64_t n,
+                            const uint64_t* riseEdgeNs, int64_t nb, ShdFlowChange* out,
+                            int64_t cap, ShdImpactTotals* totals, uint64_t* riseCount,
+                            uint64_t* riseWeight /* u64[nb + 1] each */,
+                            uint64_t* srcChangedWeight, uint64_t* dstChangedWeight /* u64[A] each */);
+int64_t shdtopo_flow_impact_device(Topology* a, Topology* b, const int32_t* d_srcCol,
+                                   const int32_t* d_dstCol,
+                                   const uint32_t* d_payload /* NULL: 1 each */, int64_t n,
+                                   const uint64_t* riseEdgeNs, int64_t nb, ShdFlowChange* out,
+                                   int64_t cap, ShdImpactTotals* totals, uint64_t* riseCount,
+                                   uint64_t* riseWeight, uint64_t* srcChangedWeight,
+                                   uint64_t* dstChangedWeight, void* stream);
+int shdtopo_flow_impact_stats(Topology* a, ShdImpactStats* out);
+
 /* Test hook: the device graph preparation (topo_prep.hip) read back -- perm
  * int32[V] (relabelled -> original vertex), rowptr u32[V+1], the adjacency columns u32[2E']
  * (relabelled ids, rows ascending by neighbour), pi f64[V] (= d(h0, .), relabelled ids) and the

@@ -126,6 +126,24 @@ class ShdDiffStats(ctypes.Structure):
                 ("bytes_read", i64)]
 
 
+class ShdFlowChange(ctypes.Structure):
+    _fields_ = [("flow", i64), ("lat0", dbl), ("lat1", dbl), ("rel0", dbl), ("rel1", dbl),
+                ("hops0", ctypes.c_uint16), ("hops1", ctypes.c_uint16), ("kind", u32)]
+
+
+class ShdImpactTotals(ctypes.Structure):
+    _fields_ = [("flows", i64), ("compared", i64), ("unattached", i64), ("changed", i64),
+                ("weight", u64), ("changedWeight", u64), ("kindCount", u64 * 4),
+                ("kindWeight", u64 * 4), ("delayRiseNs", u64), ("delayFallNs", u64),
+                ("hopsRise", u64), ("hopsFall", u64), ("worstRise", dbl), ("worstFlow", i64)]
+
+
+class ShdImpactStats(ctypes.Structure):
+    _fields_ = [("total_ms", dbl), ("resolve_ms", dbl), ("kernel_ms", dbl), ("fill_ms", dbl),
+                ("flows", i64), ("changed", i64), ("words_skipped", i64), ("bytes_model", i64),
+                ("tile_flows", i64)]
+
+
 class ShdSynthParams(ctypes.Structure):
     _fields_ = [("seed", u64), ("n_routers", i64), ("n_poi", i64), ("n_edges", i64),
                 ("integer_latency", ctypes.c_int), ("alpha", dbl), ("directed", ctypes.c_int)]
@@ -200,6 +218,9 @@ SIGNATURES = {
     "shdtopo_edge_origin": (i64, [P, P, i64]),
     "shdtopo_table_diff": (i64, [P, P, P, i64, P, P, P, P]),
     "shdtopo_table_diff_stats": (ctypes.c_int, [P, P]),
+    "shdtopo_flow_impact": (i64, [P, P, P, P, P, i64, P, i64, P, i64, P, P, P, P, P]),
+    "shdtopo_flow_impact_device": (i64, [P, P, P, P, P, i64, P, i64, P, i64, P, P, P, P, P, P]),
+    "shdtopo_flow_impact_stats": (ctypes.c_int, [P, P]),
     "shdtopo_test_segsort": (ctypes.c_int, [P, i64, P, i64, ctypes.c_int, P, P]),
     "shdtopo_test_batch_layout": (ctypes.c_int, [P, i64, dbl, ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_int, P, P, P]),

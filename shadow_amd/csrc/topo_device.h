@@ -655,6 +655,62 @@ hipError_t launch_diff_count(const DiffTables& t, int64_t* rowChanged, double* r
 hipError_t launch_diff_fill(const DiffTables& t, const int64_t* rowChanged, const int64_t* rowOff,
                             DiffRec* out, int64_t cap, hipStream_t stream);
 
+// ---- flow impact (topo_impact.hip): the changed flows of a set of column pairs ----
+// one changed flow: the device image of ShdFlowChange (include/shd_topology_abi.h); hops =
+// hops0 | hops1 << 16
+struct __attribute__((aligned(16))) ImpactRec {
+    int64_t flow;
+    double lat0, lat1, rel0, rel1;
+    uint32_t hops, kind;
+};
+// the u64 totals of one call (zeroed by the caller)
+enum {
+    IT_COMPARED = 0, IT_UNATTACHED, IT_CHANGED, IT_KIND_COUNT,  // (4 kind bits)
+    IT_WEIGHT = IT_KIND_COUNT + 4, IT_CHANGED_WEIGHT, IT_KIND_WEIGHT,
+    IT_DELAY_RISE = IT_KIND_WEIGHT + 4, IT_DELAY_FALL, IT_HOPS_RISE, IT_HOPS_FALL,
+    IT_COUNT
+};
+constexpr int kImpactMaxEdges = 1024;
+// the fill pass's count of the words it gathered for: kImpactShards counters, each on a 64-B line
+// of its own (one counter for every wavefront's add would serialise the pass on that address)
+constexpr int kImpactShards = 64, kImpactShardStride = 8;
+// The flows of one call and what the count pass writes.  Tile blk = flows [blk T, (blk + 1) T),
+// T = impact_tile_flows(); words has T / 64 words per tile, word k / 64 = the changed flows of
+// [64 (k / 64), + 64) (every word of every tile is written); tileChanged / tileRise / tileFlow have
+// one entry per tile: its changed flows, its largest lat1 - lat0 over the flows whose latency rose
+// and the lowest flow reaching it (0.0 / -1: none).  hist = u64[2 (nb + 1)], counts then weights;
+// srcW / dstW = u64[A] or NULL.
+struct ImpactFlows {
+    const int32_t* src = nullptr;
+    const int32_t* dst = nullptr;
+    int64_t n = 0;
+    const unsigned long long* edges = nullptr;
+    int32_t nb = 0;
+};
+struct ImpactOut {
+    unsigned long long* words = nullptr;
+    int64_t* tileChanged = nullptr;
+    double* tileRise = nullptr;
+    int64_t* tileFlow = nullptr;
+    unsigned long long* tot = nullptr;
+    unsigned long long* hist = nullptr;
+    unsigned long long* srcW = nullptr;
+    unsigned long long* dstW = nullptr;
+};
+int64_t impact_tile_flows();
+// Count: the weights are w64 (the host variant), else w32 (a packet window's payload), else 1.
+hipError_t launch_impact_count(const DiffTables& t, const ImpactFlows& f,
+                               const unsigned long long* w64, const uint32_t* w32,
+                               const ImpactOut& o, hipStream_t stream);
+// Fill: the changed flows' records at out[tileOff[blk] + rank in the tile] (tileOff: the
+// exclusive scan of tileChanged); records at or past cap are not written.  gathered (u64
+// [kImpactShards x kImpactShardStride], zeroed by the caller): the words gathered for, summed
+// over the shards.
+hipError_t launch_impact_fill(const DiffTables& t, const ImpactFlows& f,
+                              const unsigned long long* words, const int64_t* tileChanged,
+                              const int64_t* tileOff, ImpactRec* out, int64_t cap,
+                              unsigned long long* gathered, hipStream_t stream);
+
 hipError_t launch_pair_table_complete(int A, int64_t row0, int64_t rows, const double* elatAA,
                                       const double* elossAA, const double* vlossA, double2* out_lr,
                                       uint16_t* out_hops, double* out_rowmin,

@@ -128,6 +128,7 @@ struct _Topology {
     std::vector<uint8_t> failedVertex;
     bool preChecked = false;
     ShdDiffStats diffStats{};  // table diff (shdtopo_table_diff, topo_diff.hip): first argument's
+    ShdImpactStats impactStats{};  // flow impact (shdtopo_flow_impact, topo_impact.hip): likewise
 
     // options ("abort_on_error" and "lazy" are read by getters on worker threads without a lock)
     std::atomic<bool> abortOnError{true};
@@ -532,6 +533,11 @@ ReplayCSR replay_csr(Topology* top);
 ReplayWs replay_ws(Topology* top);
 std::vector<double> source_shifts(Topology* top, const uint32_t* s, int64_t n, double delta);
 std::vector<double> source_h0_seeds(Topology* top, const uint32_t* s, int64_t n);
+// the table of the current attached set: whether it stands, its arrays, and its build
+bool table_current(Topology* top);
+const double2* tab_lr(const Topology* top);
+const uint16_t* tab_hops(const Topology* top);
+int ensure_table(Topology* top);
 
 // the *_stats getters: the last call's counters, under the build lock
 template <class S>
@@ -565,6 +571,11 @@ inline int bin_add(uint64_t t0, uint64_t binNs, int64_t nbins, uint64_t* bins, u
     if (outside) outside[2 * row + 1] += w;
     return 2;
 }
+
+// The requests' vertices: both ends on a vertex of the current attached set, else -1; returns the
+// requests with both.
+int64_t resolve_requests(Topology* top, const uint32_t* srcIP, const uint32_t* dstIP, int64_t n,
+                         std::vector<int32_t>& sv, std::vector<int32_t>& dv);
 
 // the watch lists and the bin geometry of a timeline call or a monitor; *rows = 2 ne + nv
 bool watch_bins_ok(Topology* top, const int32_t* watchEdge, int64_t ne, const int32_t* watchVertex,

@@ -88,6 +88,12 @@ TABLE_CHANGE_DTYPE = np.dtype([("srcCol", np.int32), ("dstCol", np.int32), ("lat
                                ("hops0", np.uint16), ("hops1", np.uint16), ("kind", np.uint32)])
 
 
+# one record of Topology.flow_impact (ShdFlowChange)
+FLOW_CHANGE_DTYPE = np.dtype([("flow", np.int64), ("lat0", np.float64), ("lat1", np.float64),
+                              ("rel0", np.float64), ("rel1", np.float64), ("hops0", np.uint16),
+                              ("hops1", np.uint16), ("kind", np.uint32)])
+
+
 def crossings_by_watch(result):
     """Invert a Topology.link_crossings result into {watch index: flow indices} -- every watch of
     the call, the flows ascending, a flow once per record (host side: the records are already in
@@ -652,6 +658,87 @@ class Topology:
         if self._lib.shdtopo_table_diff_stats(self._h, ctypes.byref(s)) != 0:
             raise RuntimeError("shdtopo_table_diff_stats failed")
         return {k: getattr(s, k) for k, _ in L.ShdDiffStats._fields_}
+
+    def _flow_impact(self, what, call, n, rise_edges_ns, cap):
+        """The outputs of one shdtopo_flow_impact* call; call(edges, nb, out, cap, totals,
+        rise_count, rise_weight, src_w, dst_w) makes it."""
+        edges = np.ascontiguousarray(rise_edges_ns, dtype=np.uint64).reshape(-1)
+        nb = len(edges)
+        pe = _p(edges) if nb else None
+        if cap is None:
+            cap = int(call(pe, nb, None, 0, None, None, None, None, None))
+            if cap < 0:
+                raise RuntimeError("%s failed: %d" % (what, cap), cap)
+        cap = int(cap)
+        A = int(self._lib.shdtopo_num_attached(self._h))
+        tt = L.ShdImpactTotals()
+        hist = np.zeros((2, nb + 1), np.uint64)
+        colw = np.zeros((2, max(A, 1)), np.uint64)
+        records = np.zeros(max(cap, 1), FLOW_CHANGE_DTYPE)
+        total = int(call(pe, nb, _p(records) if cap else None, cap, ctypes.byref(tt),
+                         _p(hist[0]), _p(hist[1]), _p(colw[0]), _p(colw[1])))
+        if total < 0:
+            raise RuntimeError("%s failed: %d" % (what, total), total)
+        totals = {}
+        for k, _ in L.ShdImpactTotals._fields_:
+            v = getattr(tt, k)
+            totals[k] = np.array(list(v), np.uint64) if k.startswith("kind") else v
+        return {"total": total, "records": records[:min(total, cap)], "totals": totals,
+                "rise_count": hist[0], "rise_weight": hist[1],
+                "src_changed_weight": colw[0][:A], "dst_changed_weight": colw[1][:A]}
+
+    def flow_impact(self, other, src_ips, dst_ips, weight=None, rise_edges_ns=(), cap=None):
+        """shdtopo_flow_impact: what changes for the flows (src_ips[i] -> dst_ips[i], weight[i];
+        None: 1 each) between this topology's table (lat0 / rel0 / hops0) and ``other``'s, joined
+        on the device; both must have the same attached vertices.  Returns a dict: ``total``, the
+        number of changed flows; ``records`` (FLOW_CHANGE_DTYPE), the first min(total, cap) of
+        them in ascending flow order (cap=None sizes the buffer with a cap = 0 call first);
+        ``totals``, the fields of ShdImpactTotals (kindCount / kindWeight as uint64[4]);
+        ``rise_count`` / ``rise_weight`` uint64[len(rise_edges_ns) + 1], the histogram of the
+        delay rises in ns (a rise equal to an edge goes to the upper bin);
+        ``src_changed_weight`` / ``dst_changed_weight`` uint64[A], the weight of the changed flows
+        leaving / entering each column.  Every sum is a u64 that wraps."""
+        s = np.ascontiguousarray(src_ips, dtype=np.uint32)
+        d = np.ascontiguousarray(dst_ips, dtype=np.uint32)
+        if s.shape != d.shape or s.ndim != 1:
+            raise ValueError("src_ips and dst_ips must be 1-D and of one length")
+        w = None
+        if weight is not None:
+            w = np.ascontiguousarray(weight, dtype=np.uint64)
+            if w.shape != s.shape:
+                raise ValueError("weight must have one entry per flow")
+        n = len(s)
+
+        def call(*outs):
+            return self._lib.shdtopo_flow_impact(
+                self._h, other._h, _p(s) if n else None, _p(d) if n else None,
+                _p(w) if w is not None else None, n, *outs)
+        return self._flow_impact("shdtopo_flow_impact", call, n, rise_edges_ns, cap)
+
+    def flow_impact_device(self, other, src_col, dst_col, payload=None, rise_edges_ns=(), cap=None,
+                           stream=0):
+        """shdtopo_flow_impact_device: flow_impact on the device arrays of route_batch_device
+        (torch tensors used as plain HBM buffers: int32 columns, a column outside [0, A) is
+        unattached; uint32-sized payload as the weight, None: 1 each).  The kernels run on
+        ``stream``; the call returns when they are done."""
+        n = int(src_col.numel())
+        if int(dst_col.numel()) != n or (payload is not None and int(payload.numel()) != n):
+            raise ValueError("the columns and the payload must be of one length")
+
+        def call(*outs):
+            return self._lib.shdtopo_flow_impact_device(
+                self._h, other._h, src_col.data_ptr() if n else None,
+                dst_col.data_ptr() if n else None,
+                payload.data_ptr() if payload is not None else None, n, *outs, stream or None)
+        return self._flow_impact("shdtopo_flow_impact_device", call, n, rise_edges_ns, cap)
+
+    def flow_impact_stats(self):
+        """The last flow_impact's own counters, kept by its first topology
+        (shdtopo_flow_impact_stats); ``tile_flows`` is the build's tile, 256 x U flows."""
+        s = L.ShdImpactStats()
+        if self._lib.shdtopo_flow_impact_stats(self._h, ctypes.byref(s)) != 0:
+            raise RuntimeError("shdtopo_flow_impact_stats failed")
+        return {k: getattr(s, k) for k, _ in L.ShdImpactStats._fields_}
 
     def write_graphml(self, path):
         if self._lib.shdtopo_write_graphml(self._h, path.encode()) != 0:
