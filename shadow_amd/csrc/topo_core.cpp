@@ -272,6 +272,9 @@ int dev_init(Topology* top) {
     HIPCHK(hipEventCreate(&top->evp1));
     tmark("events");
     HIPCHK(top->d_stats.ensure(ST_COUNT));
+    // (a build zeroes the block again; a table installed by shdtopo_bind_table* has none before
+    // its first packet route adds to ST_ROUTE_BAD)
+    HIPCHK(hipMemset(top->d_stats.p, 0, sizeof(unsigned long long) * ST_COUNT));
     tmark("stats buffer");
     for (hipStream_t& c : top->cstream) HIPCHK(hipStreamCreateWithFlags(&c, hipStreamNonBlocking));
     {

@@ -76,16 +76,17 @@ _KEYS = ('<key attr.name="packetloss" attr.type="double" for="edge" id="d9" />'
 
 
 def graphml_doc(nodes, edges, directed=False):
-    """GraphML text in the bundled files' key schema.  nodes: (id, type, loss);
-    edges: (src, dst, latency, loss)."""
+    """GraphML text in the bundled files' key schema.  nodes: (id, type, loss) or
+    (id, type, loss, ip) -- the ip attribute is 0.0.0.0 when not given; edges: (src, dst,
+    latency, loss)."""
     out = ['<?xml version="1.0" encoding="utf-8"?><graphml '
            'xmlns="http://graphml.graphdrawing.org/xmlns">', _KEYS,
            '<graph edgedefault="%s">' % ("directed" if directed else "undirected")]
-    for nid, typ, loss in nodes:
-        out.append('<node id="%s"><data key="d0">%r</data><data key="d1">0.0.0.0</data>'
+    for nid, typ, loss, *ip in nodes:
+        out.append('<node id="%s"><data key="d0">%r</data><data key="d1">%s</data>'
                    '<data key="d2">US</data><data key="d3">10240</data>'
                    '<data key="d4">10240</data><data key="d5">%s</data></node>'
-                   % (nid, float(loss), typ))
+                   % (nid, float(loss), ip[0] if ip else "0.0.0.0", typ))
     for a, b, lat, loss in edges:
         out.append('<edge source="%s" target="%s"><data key="d7">%r</data>'
                    '<data key="d8">0</data><data key="d9">%r</data></edge>'

@@ -81,7 +81,9 @@ def expected_impact(t0, t1, sc, dc, w, edges):
     rec["hops0"], rec["hops1"], rec["kind"] = h0[idx], h1[idx], kind[idx]
     d0, d1 = delay_ns(np.where(ok, l0, 0.0)), delay_ns(np.where(ok, l1, 0.0))
     up, down = (d1 - d0)[rose], (d0 - d1)[fell]
-    hup, hdown = h1 > h0, h1 < h0  # (both imply "changed")
+    # (both imply "changed"; a flow that is not compared gathered pair (0, 0) above and counts for
+    # nothing: "Flow i is compared when both ends are columns", include/shd_topology_abi.h)
+    hup, hdown = ok & (h1 > h0), ok & (h1 < h0)
     hd = lambda m, x, y: (x[m].astype(U64) - y[m].astype(U64)) * w[m]
     bits = (ROSE, FELL, REL, HOPS)
     totals = {
