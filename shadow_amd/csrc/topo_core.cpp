@@ -212,8 +212,6 @@ bool check_graph(Topology* top) {
     return true;
 }
 
-void start_device_init(Topology* top);
-
 Topology* finish_new(Topology* top) {
     if (!check_graph(top)) {
         topology_free(top);  // joins the device-init thread, releases the device
@@ -413,9 +411,6 @@ int upload_csr_impl(Topology* top) {
     HostGraph& g = top->g;
     const int32_t V = g.V;
     using clk = std::chrono::steady_clock;
-    auto ms_since = [](clk::time_point t) {
-        return std::chrono::duration<double, std::milli>(clk::now() - t).count();
-    };
     double host_ms = 0.0, copy_ms = 0.0;
     top->hp = std::make_shared<HostPrep>();
     top->csrHostRuns++;
@@ -2587,235 +2582,6 @@ int shdtopo_export_graph(Topology* top, int32_t* eu, int32_t* ev, double* elat, 
 int shdtopo_write_graphml(Topology* top, const char* path) {
     if (!top || !path) return -1;
     return graphml_write_file(top->g, path) ? 0 : -1;
-}
-
-// ---- link failure what-if (include/shd_topology_abi.h) ----
-
-Topology* shdtopo_derive_without(Topology* top, const int32_t* failEdge, int64_t ne,
-                                 const int32_t* failVertex, int64_t nv, int32_t* err) {
-    auto fail = [&](int32_t code) -> Topology* {
-        if (err) *err = code;
-        return nullptr;
-    };
-    if (err) *err = 0;
-    if (!top || ne < 0 || nv < 0 || (ne > 0 && !failEdge) || (nv > 0 && !failVertex))
-        return fail(-1);
-    using clk = std::chrono::steady_clock;
-    auto tq = clk::now();
-    auto lap = [&]() {
-        const auto t = clk::now();
-        const double ms = std::chrono::duration<double, std::milli>(t - tq).count();
-        tq = t;
-        return ms;
-    };
-    const HostGraph& pg = top->g;
-    // everything is validated on the parent's arrays before the child exists: an error allocates
-    // no page-locked memory and starts no device thread
-    std::vector<uint8_t> dropE((size_t)pg.E, 0), dropV((size_t)pg.V, 0);
-    for (int64_t i = 0; i < ne; i++) {
-        if (failEdge[i] < 0 || failEdge[i] >= pg.E) return fail(-1);
-        dropE[(size_t)failEdge[i]] = 1;
-    }
-    for (int64_t i = 0; i < nv; i++)
-        if (failVertex[i] < 0 || failVertex[i] >= pg.V) return fail(-1);
-    int device = 0;
-    {
-        std::lock_guard<std::mutex> lk(top->buildMu);
-        device = top->device;
-    }
-    std::vector<std::pair<uint32_t, int32_t>> hosts;
-    {
-        std::shared_lock<std::shared_mutex> lk(top->ipMu);
-        for (int64_t i = 0; i < nv; i++)
-            if (top->hostsOn[(size_t)failVertex[i]] > 0) {
-                CRITICAL("vertex %d has %u hosts attached and cannot be failed", failVertex[i],
-                         top->hostsOn[(size_t)failVertex[i]]);
-                return fail(-2);
-            }
-        hosts.assign(top->virtualIP.begin(), top->virtualIP.end());
-    }
-    std::sort(hosts.begin(), hosts.end());
-    bool anyV = !top->failedVertex.empty();
-    if (anyV) dropV = top->failedVertex;  // (isolated already: their edges are gone)
-    for (int64_t i = 0; i < nv; i++) {
-        dropV[(size_t)failVertex[i]] = 1;
-        anyV = true;
-    }
-    if (anyV)
-        for (int64_t e = 0; e < pg.E; e++)
-            if (dropV[(size_t)pg.eu[(size_t)e]] || dropV[(size_t)pg.ev[(size_t)e]])
-                dropE[(size_t)e] = 1;
-    const int64_t cut = cut_off_vertices(pg, dropE, dropV);
-    if (cut != 0) {
-        if (cut < 0)
-            CRITICAL("the failing set leaves no vertex");
-        else
-            CRITICAL("the failing set cuts off %lld vertices: what remains must be but is not "
-                     "strongly connected (partitioned networks are not modelled)",
-                     (long long)cut);
-        return fail(-3);
-    }
-    const double validateMs = lap();
-    Topology* c = new Topology();
-    c->device = device;
-    c->abortOnError = top->abortOnError.load();
-    c->lazy = top->lazy.load();
-    start_device_init(c);  // the device initialises while the graph is copied and checked
-    std::vector<int32_t> origin;
-    derive_graph(pg, dropE, c->g, origin);
-    if (!top->edgeOrigin.empty())
-        for (int32_t& e : origin) e = top->edgeOrigin[(size_t)e];
-    c->edgeOrigin = std::move(origin);
-    if (anyV) c->failedVertex = std::move(dropV);
-    c->preChecked = true;
-    const double copyMs = lap();
-    c = finish_new(c);
-    if (!c) return fail(-1);
-    if (!getenv("SHDTOPO_NO_LOAD_PREP")) start_graph_prep(c, true);
-    const double checkMs = lap();
-    for (const auto& h : hosts) do_attach(c, h.first, h.second, nullptr, nullptr);
-    MESSAGE("derived topology without %lld edges: validation and connectivity %.1f, copy %.1f, "
-            "graph checks %.1f, %zu hosts carried over %.1f ms",
-            (long long)(pg.E - c->g.E), validateMs, copyMs, checkMs, hosts.size(), lap());
-    return c;
-}
-
-int64_t shdtopo_edge_origin(Topology* top, int32_t* origin, int64_t cap) {
-    if (!top) return -1;
-    const int64_t E = top->g.E;
-    if (origin && cap >= E) {
-        if (top->edgeOrigin.empty())
-            for (int64_t e = 0; e < E; e++) origin[e] = (int32_t)e;
-        else
-            memcpy(origin, top->edgeOrigin.data(), 4 * (size_t)E);
-    }
-    return E;
-}
-
-}  // extern "C"
-
-namespace {
-
-static_assert(sizeof(ShdTableChange) == 48 && sizeof(DiffRec) == sizeof(ShdTableChange) &&
-                  offsetof(ShdTableChange, hops0) == 40 && offsetof(ShdTableChange, kind) == 44,
-              "DiffRec is the device image of ShdTableChange");
-
-// the diff of two current tables with equal attached sets; the caller holds both build locks
-int64_t diff_locked(Topology* a, Topology* b, ShdTableChange* out, int64_t cap,
-                    uint64_t* kindCount, uint32_t* rowChanged, double* rowWorstRise,
-                    int32_t* rowWorstCol, ShdDiffStats* ds) {
-    const int64_t A = a->A;
-    ds->pairs = A * A;
-    if (kindCount) std::fill(kindCount, kindCount + 4, (uint64_t)0);
-    if (rowChanged) std::fill(rowChanged, rowChanged + (size_t)A, 0u);
-    if (rowWorstRise) std::fill(rowWorstRise, rowWorstRise + (size_t)A, 0.0);
-    if (rowWorstCol) std::fill(rowWorstCol, rowWorstCol + (size_t)A, (int32_t)-1);
-    if (a == b || A == 0) return 0;
-    if (a->devId != b->devId) return -6;
-    int r = dev_init(a);  // this thread's HIP device = the tables'
-    if (r) return r;
-    hipStream_t st = a->stream;
-    HIPCHK(hipStreamSynchronize(b->stream));  // (b's table was written on b's stream)
-    DiffTables t;
-    t.lr0 = tab_lr(a);
-    t.lr1 = tab_lr(b);
-    t.hops0 = tab_hops(a);
-    t.hops1 = tab_hops(b);
-    t.A = (int32_t)A;
-    DevBuf<int64_t> d_cnt, d_off;
-    DevBuf<double> d_rise;
-    DevBuf<int32_t> d_col;
-    DevBuf<unsigned long long> d_kc;
-    DevBuf<DiffRec> d_out;
-    HIPCHK(d_cnt.ensure((size_t)A + 1));
-    HIPCHK(d_off.ensure((size_t)A + 1));
-    HIPCHK(d_rise.ensure((size_t)A));
-    HIPCHK(d_col.ensure((size_t)A));
-    HIPCHK(d_kc.ensure(4));
-    struct Events {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Events() {
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-        }
-    } ev;
-    HIPCHK(hipEventCreate(&ev.e0));
-    HIPCHK(hipEventCreate(&ev.e1));
-    HIPCHK(hipMemsetAsync(d_kc.p, 0, 4 * sizeof(unsigned long long), st));
-    HIPCHK(hipMemsetAsync(d_cnt.p + A, 0, sizeof(int64_t), st));
-    HIPCHK(hipEventRecord(ev.e0, st));
-    HIPCHK(launch_diff_count(t, d_cnt.p, d_rise.p, d_col.p, d_kc.p, st));
-    HIPCHK(trace_exclusive_scan(d_cnt.p, d_off.p, A + 1, st));  // (synchronises st)
-    std::vector<int64_t> cnt((size_t)A), off((size_t)A + 1);
-    HIPCHK(hipMemcpy(cnt.data(), d_cnt.p, sizeof(int64_t) * (size_t)A, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(off.data(), d_off.p, sizeof(int64_t) * ((size_t)A + 1), hipMemcpyDeviceToHost));
-    const int64_t total = off[(size_t)A];
-    const int64_t nw = std::min(total, cap);
-    int64_t filled = 0;  // rows the fill pass walks
-    if (nw > 0) {
-        HIPCHK(d_out.ensure((size_t)nw));
-        HIPCHK(launch_diff_fill(t, d_cnt.p, d_off.p, d_out.p, cap, st));
-        for (int64_t s = 0; s < A; s++) filled += cnt[(size_t)s] > 0 && off[(size_t)s] < cap ? 1 : 0;
-    }
-    HIPCHK(hipEventRecord(ev.e1, st));
-    HIPCHK(hipStreamSynchronize(st));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
-    ds->kernel_ms = ms;
-    ds->bytes_read = 36 * (A * A + filled * A);
-    if (nw > 0) HIPCHK(hipMemcpy(out, d_out.p, sizeof(DiffRec) * (size_t)nw, hipMemcpyDeviceToHost));
-    if (kindCount) HIPCHK(hipMemcpy(kindCount, d_kc.p, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (rowChanged)
-        for (int64_t s = 0; s < A; s++) rowChanged[s] = (uint32_t)cnt[(size_t)s];
-    if (rowWorstRise)
-        HIPCHK(hipMemcpy(rowWorstRise, d_rise.p, sizeof(double) * (size_t)A, hipMemcpyDeviceToHost));
-    if (rowWorstCol)
-        HIPCHK(hipMemcpy(rowWorstCol, d_col.p, sizeof(int32_t) * (size_t)A, hipMemcpyDeviceToHost));
-    return total;
-}
-
-}  // namespace
-
-extern "C" {
-
-int64_t shdtopo_table_diff(Topology* a, Topology* b, ShdTableChange* out, int64_t cap,
-                           uint64_t kindCount[4], uint32_t* rowChanged, double* rowWorstRise,
-                           int32_t* rowWorstCol) {
-    if (!a || !b || cap < 0 || (cap > 0 && !out)) return -1;
-    const auto t0 = std::chrono::steady_clock::now();
-    Topology* lo = std::less<Topology*>()(b, a) ? b : a;
-    Topology* hi = lo == a ? b : a;
-    for (int attempt = 0; attempt < 4; attempt++) {
-        {
-            // both build locks, the lower address first
-            std::unique_lock<std::mutex> l1(lo->buildMu);
-            std::unique_lock<std::mutex> l2;
-            if (hi != lo) l2 = std::unique_lock<std::mutex>(hi->buildMu);
-            compute_geometry(a);
-            if (a != b) compute_geometry(b);
-            if (a->attached != b->attached) return -4;
-            if (table_current(a) && table_current(b)) {
-                ShdDiffStats ds{};
-                const int64_t total = diff_locked(a, b, out, cap, kindCount, rowChanged,
-                                                  rowWorstRise, rowWorstCol, &ds);
-                ds.changed = total < 0 ? 0 : total;
-                ds.total_ms = std::chrono::duration<double, std::milli>(
-                    std::chrono::steady_clock::now() - t0).count();
-                a->diffStats = ds;
-                return total;
-            }
-        }
-        // a missing or stale table is built as by shdtopo_build (it takes the build lock itself)
-        int r = ensure_table(a);
-        if (!r && a != b) r = ensure_table(b);
-        if (r) return r;
-    }
-    CRITICAL("the attached sets keep changing while the tables are compared");
-    return -5;
-}
-
-int shdtopo_table_diff_stats(Topology* a, ShdDiffStats* out) {
-    return copy_stats(a, &_Topology::diffStats, out);
 }
 
 int shdtopo_synth_packets(Topology* top, uint64_t seed, int64_t n_hosts, int64_t n_packets,

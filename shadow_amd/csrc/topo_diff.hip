@@ -28,6 +28,7 @@
 #include <cstdint>
 
 #include "topo_dev_common.h"
+#include "topo_paircmp.h"
 
 namespace shdtopo {
 
@@ -40,20 +41,6 @@ constexpr int kTB = 256;
 constexpr int kNW = kTB / 64;
 
 static_assert(sizeof(DiffRec) == 48, "DiffRec is three 16-B stores");
-
-// kind bits of pair (x0, h0) -> (x1, h1); 0: unchanged
-__device__ __forceinline__ uint32_t diff_kind(const double2& x0, const double2& x1, uint32_t h0,
-                                              uint32_t h1) {
-    uint32_t k = 0;
-    if (d2bits(x0.x) != d2bits(x1.x)) k |= x1.x > x0.x ? kDiffLatRose : (x1.x < x0.x ? kDiffLatFell : 0u);
-    if (d2bits(x0.y) != d2bits(x1.y)) k |= kDiffRel;
-    if (h0 != h1) k |= kDiffHops;
-    return k;
-}
-__device__ __forceinline__ bool diff_changed(const double2& x0, const double2& x1, uint32_t h0,
-                                             uint32_t h1) {
-    return d2bits(x0.x) != d2bits(x1.x) || d2bits(x0.y) != d2bits(x1.y) || h0 != h1;
-}
 
 __global__ __launch_bounds__(kTB) void diff_count_kernel(DiffTables t, int64_t* rowChanged,
                                                          double* rowWorstRise,
@@ -73,9 +60,9 @@ __global__ __launch_bounds__(kTB) void diff_count_kernel(DiffTables t, int64_t* 
     for (int32_t d = (int32_t)threadIdx.x; d < A; d += kTB) {
         const double2 x0 = t.lr0[base + (size_t)d], x1 = t.lr1[base + (size_t)d];
         const uint32_t h0 = t.hops0[base + (size_t)d], h1 = t.hops1[base + (size_t)d];
-        if (!diff_changed(x0, x1, h0, h1)) continue;
+        if (!pair_changed(x0, x1, h0, h1)) continue;
         changed++;
-        const uint32_t k = diff_kind(x0, x1, h0, h1);
+        const uint32_t k = pair_kind(x0, x1, h0, h1);
 #pragma unroll
         for (int i = 0; i < 4; i++) kc[i] += (k >> i) & 1u;
         if (k & kDiffLatRose) {
@@ -92,13 +79,8 @@ __global__ __launch_bounds__(kTB) void diff_count_kernel(DiffTables t, int64_t* 
         changed += __shfl_xor(changed, o, 64);
 #pragma unroll
         for (int i = 0; i < 4; i++) kc[i] += __shfl_xor(kc[i], o, 64);
-        const double r = __shfl_xor(rise, o, 64);
-        const int32_t c = __shfl_xor(col, o, 64);
-        if (c >= 0 && (col < 0 || r > rise || (r == rise && c < col))) {
-            rise = r;
-            col = c;
-        }
     }
+    wave_worst_rise(rise, col);
     if (lane == 0) {
         if (changed) atomicAdd(&s_cnt[4], changed);
 #pragma unroll
@@ -113,7 +95,7 @@ __global__ __launch_bounds__(kTB) void diff_count_kernel(DiffTables t, int64_t* 
         for (int w = 1; w < kNW; w++) {
             const double r = s_rise[w];
             const int32_t c = s_col[w];
-            if (c >= 0 && (col < 0 || r > rise || (r == rise && c < col))) {
+            if (worse_rise(r, c, rise, col)) {
                 rise = r;
                 col = c;
             }
@@ -146,7 +128,7 @@ __global__ __launch_bounds__(kTB) void diff_fill_kernel(DiffTables t, const int6
             x1 = t.lr1[base + (size_t)d];
             h0 = t.hops0[base + (size_t)d];
             h1 = t.hops1[base + (size_t)d];
-            ch = diff_changed(x0, x1, h0, h1);
+            ch = pair_changed(x0, x1, h0, h1);
         }
         const u64 m = __ballot(ch);
         if (lane == 0) s_wave[wid] = (uint32_t)__popcll(m);
@@ -169,7 +151,7 @@ __global__ __launch_bounds__(kTB) void diff_fill_kernel(DiffTables t, const int6
                 r.rel0 = x0.y;
                 r.rel1 = x1.y;
                 r.hops = (h0 & 0xFFFFu) | (h1 << 16);
-                r.kind = diff_kind(x0, x1, h0, h1);
+                r.kind = pair_kind(x0, x1, h0, h1);
                 out[p] = r;
             }
         }

@@ -267,7 +267,7 @@ int group_replay_requests(Topology* top, const std::vector<int32_t>& sv,
     HIPCHK(hipMemcpy(R.d_rsrc.p, rsrc.data(), 4 * nv, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(R.d_rdst.p, rdst.data(), 4 * nv, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(R.d_ridx.p, order.data(), 4 * nv, hipMemcpyHostToDevice));
-    for (hipEvent_t& x : R.ev.e) HIPCHK(hipEventCreate(&x));
+    CHK(R.ev.create());
     R.ids = TraceIds{top->d_tperm.p, top->d_reid.p, top->d_selfEid.p};
     return 0;
 }

@@ -1,7 +1,7 @@
 // topo_host.h -- what the host units of libshdtopo (topo_core.cpp, topo_build.cpp, topo_flows.cpp,
-// topo_monitor_host.cpp) share: logging, DevBuf, struct _Topology, the core functions the table
-// build and the flow analysis call and the flow analysis' own shared parts.  Included by the
-// .cpp units only.
+// topo_monitor_host.cpp, topo_whatif.cpp) share: logging, DevBuf, DevEvents, struct _Topology, the
+// core functions the table build, the flow analysis and the what-if family call and the flow
+// analysis' own shared parts.  Included by the .cpp units only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -67,6 +67,25 @@ struct DevBuf {
         return e;
     }
 };
+
+// N events of one call's own, destroyed with it (hidden: the library exports no instantiation)
+template <int N>
+struct __attribute__((visibility("hidden"))) DevEvents {
+    hipEvent_t e[N] = {};
+    int create() {
+        for (hipEvent_t& x : e) HIPCHK(hipEventCreate(&x));
+        return 0;
+    }
+    ~DevEvents() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+};
+
+// wall-clock milliseconds since t
+inline double ms_since(std::chrono::steady_clock::time_point t) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
 
 // Open-addressing IP -> vertex table read by the getters without a lock (Shadow calls them from
 // every worker thread, shd-worker.c:179-203; the reference takes virtualIPLock per lookup,
@@ -538,6 +557,13 @@ bool table_current(Topology* top);
 const double2* tab_lr(const Topology* top);
 const uint16_t* tab_hops(const Topology* top);
 int ensure_table(Topology* top);
+// ... and what a derived topology is made with (shdtopo_derive_without, topo_whatif.cpp): the
+// graph checks of a new topology (nullptr: it was freed), its background device init and graph
+// preparation, one host onto vertex v
+Topology* finish_new(Topology* top);
+void start_device_init(Topology* top);
+void start_graph_prep(Topology* top, bool onLoad);
+void do_attach(Topology* top, uint32_t ip, int32_t v, uint64_t* bwDownOut, uint64_t* bwUpOut);
 
 // the *_stats getters: the last call's counters, under the build lock
 template <class S>
@@ -596,15 +622,9 @@ struct TraceKeep {
         top->rslotsUse = rslotsUse;
     }
 };
-struct TraceEvents {
-    // 0 / 1 bracket a chunk's replay launch, 2 closes the chunk; 3 / 4 bracket its keep launch,
-    // 5 / 6 the pair walks' first pass
-    hipEvent_t e[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~TraceEvents() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
+// 0 / 1 bracket a chunk's replay launch, 2 closes the chunk; 3 / 4 bracket its keep launch, 5 / 6
+// the pair walks' first pass
+using TraceEvents = DevEvents<7>;
 
 // The requests of a trace or a link load grouped for the replay: those with both ends attached,
 // sorted by source (stable: request order within a source), a CSR over the distinct sources and

@@ -16,7 +16,8 @@
 //          lives in LDS (2 (nb + 1) u64) and only its non-zero bins are flushed.  The per-column
 //          weights are global u64 atomics of the changed flows.  Every sum is an integer sum that
 //          wraps: any order gives the same result.  The tile's {largest rise, lowest flow reaching
-//          it} uses a symmetric tie rule, as diff_count_kernel; the host takes the last step.
+//          it} is merged by topo_paircmp.h's rule, as in diff_count_kernel; the host takes the
+//          last step.
 //   scan   trace_exclusive_scan over the tiles' changed counts: each tile's first record;
 //   fill   the same tiling.  Every thread reads its tile's 4 U words: a changed lane's rank is the
 //          tile's offset + the popcounts of the earlier words (flow order: j-major, then
@@ -34,6 +35,7 @@
 #include <cstdint>
 
 #include "topo_dev_common.h"
+#include "topo_paircmp.h"
 
 namespace shdtopo {
 
@@ -56,28 +58,9 @@ static_assert(kU >= 1 && kU <= 8, "flows per thread");
 // LDS of the count pass (all dynamic, u64 words): the totals, the waves' {rise, flow}, the histogram
 constexpr int kLdsTot = 0, kLdsRise = IT_COUNT, kLdsFlow = kLdsRise + kNW, kLdsHist = kLdsFlow + kNW;
 
-// kind bits of pair (x0, h0) -> (x1, h1), as topo_diff.hip's diff_kind; 0: unchanged
-__device__ __forceinline__ uint32_t impact_kind(const double2& x0, const double2& x1, uint32_t h0,
-                                                uint32_t h1) {
-    uint32_t k = 0;
-    if (d2bits(x0.x) != d2bits(x1.x)) k |= x1.x > x0.x ? kDiffLatRose : (x1.x < x0.x ? kDiffLatFell : 0u);
-    if (d2bits(x0.y) != d2bits(x1.y)) k |= kDiffRel;
-    if (h0 != h1) k |= kDiffHops;
-    return k;
-}
-__device__ __forceinline__ bool impact_changed(const double2& x0, const double2& x1, uint32_t h0,
-                                               uint32_t h1) {
-    return d2bits(x0.x) != d2bits(x1.x) || d2bits(x0.y) != d2bits(x1.y) || h0 != h1;
-}
 // the packet route's delay (topo_kernels.hip).  lat is finite and >= 0: attached pairs are connected
 // (an infinite or NaN latency would make the cast undefined here as there)
 __device__ __forceinline__ u64 delay_ns(double lat) { return (u64)ceil(lat * 1000000.0); }
-
-__device__ __forceinline__ u64 wave_sum(u64 x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
 
 // the pair index of flow k (-1: an end is no column), its columns to sc / dc
 __device__ __forceinline__ int64_t flow_pair(const ImpactFlows& f, int64_t A, int64_t k,
@@ -136,8 +119,8 @@ __global__ __launch_bounds__(kTB) void impact_count_kernel(DiffTables t, ImpactF
     for (int j = 0; j < kU; j++) {
         const int64_t k = base + (int64_t)j * kTB;
         const bool ok = idx[j] >= 0;
-        const uint32_t kind = ok ? impact_kind(x0[j], x1[j], h0[j], h1[j]) : 0u;
-        const bool ch = ok && impact_changed(x0[j], x1[j], h0[j], h1[j]);
+        const uint32_t kind = ok ? pair_kind(x0[j], x1[j], h0[j], h1[j]) : 0u;
+        const bool ch = ok && pair_changed(x0[j], x1[j], h0[j], h1[j]);
         const u64 mOk = __ballot(ok), mIn = __ballot(k < f.n), m = __ballot(ch);
         if (lane == 0) o.words[(int64_t)blockIdx.x * kWords + j * kNW + wid] = m;
         nCompared += (uint32_t)__popcll(mOk);
@@ -183,26 +166,16 @@ __global__ __launch_bounds__(kTB) void impact_count_kernel(DiffTables t, ImpactF
     }
 
     // the wavefront's sums; those of the changed flows only where it has one
-    wsum = wave_sum(wsum);
+    wsum = wave_sum_u64(wsum);
     if (nChanged) {
-        chw = wave_sum(chw);
+        chw = wave_sum_u64(chw);
 #pragma unroll
-        for (int i = 0; i < 4; i++) kw[i] = wave_sum(kw[i]);
-        dRise = wave_sum(dRise);
-        dFall = wave_sum(dFall);
-        hRise = wave_sum(hRise);
-        hFall = wave_sum(hFall);
-        if (kc[0]) {  // {largest rise, lowest flow}
-#pragma unroll
-            for (int s = 32; s > 0; s >>= 1) {
-                const double r = __shfl_xor(rise, s, 64);
-                const int64_t c = __shfl_xor(flow, s, 64);
-                if (c >= 0 && (flow < 0 || r > rise || (r == rise && c < flow))) {
-                    rise = r;
-                    flow = c;
-                }
-            }
-        }
+        for (int i = 0; i < 4; i++) kw[i] = wave_sum_u64(kw[i]);
+        dRise = wave_sum_u64(dRise);
+        dFall = wave_sum_u64(dFall);
+        hRise = wave_sum_u64(hRise);
+        hFall = wave_sum_u64(hFall);
+        if (kc[0]) wave_worst_rise(rise, flow);  // {largest rise, lowest flow}
     }
     if (lane == 0) {
         auto add = [&](int i, u64 v) {
@@ -239,7 +212,7 @@ __global__ __launch_bounds__(kTB) void impact_count_kernel(DiffTables t, ImpactF
         for (int q = 1; q < kNW; q++) {
             const double r = bits2d(lds[kLdsRise + q]);
             const int64_t c = (int64_t)lds[kLdsFlow + q];
-            if (c >= 0 && (flow < 0 || r > rise || (r == rise && c < flow))) {
+            if (worse_rise(r, c, rise, flow)) {
                 rise = r;
                 flow = c;
             }
@@ -298,7 +271,7 @@ __global__ __launch_bounds__(kTB) void impact_fill_kernel(DiffTables t, ImpactFl
         r.rel0 = x0.y;
         r.rel1 = x1.y;
         r.hops = (h0 & 0xFFFFu) | (h1 << 16);
-        r.kind = impact_kind(x0, x1, h0, h1);
+        r.kind = pair_kind(x0, x1, h0, h1);
         out[p] = r;
     }
     if (lane == 0 && ng)

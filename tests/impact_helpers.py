@@ -38,10 +38,11 @@ def delay_ns(lat):
     return np.ceil(lat * 1e6).astype(U64)
 
 
-def columns_of(c, ips):
-    """Columns of the hosts' IPs in the tables of case c (-1: not attached)."""
+def columns_of(c, ips, attached=None):
+    """Columns of the hosts' IPs in the tables of case c (-1: not attached); attached: the columns'
+    vertices where they are no longer the case's."""
     vert = dict(zip(c["ips"], c["verts"]))
-    col = {int(v): k for k, v in enumerate(c["t0"][0])}
+    col = {int(v): k for k, v in enumerate(c["t0"][0] if attached is None else attached)}
     return np.array([col.get(vert.get(int(ip), -1), -1) for ip in ips], np.int32)
 
 

@@ -13,9 +13,10 @@ import pytest
 
 from helpers import host_ip
 from impact_helpers import (FLOW_CHANGE, UNATTACHED_IP, assert_impact_equal, assert_sums_equal,
-                            expected_impact, impact_flows, prefix)
+                            columns_of, expected_impact, impact_flows, prefix, usum)
 from shadow_amd import _lib
-from whatif_helpers import FELL, ROSE, assert_table_equal, case, product
+from whatif_helpers import (FELL, ROSE, assert_table_equal, attach_off_column, build_counters, case,
+                            product)
 
 pytestmark = pytest.mark.gpu
 
@@ -296,3 +297,92 @@ def test_identical_child():
         assert not got[k].any(), k
     st = top.flow_impact_stats()
     assert st["words_skipped"] == (want["flows"] + 63) // 64 and st["kernel_ms"] > 0
+
+
+# ---- the paths of the pair loop (with_current_pair, topo_whatif.cpp) the tests above do not reach:
+# ---- they build both tables first
+
+def test_impact_builds_missing_tables():
+    c, fl = case("real"), impact_flows("real")
+    top = product("real")
+    child = top.without(edges=c["fail"])
+    # no build and no getter so far: the call builds both tables
+    assert_impact_equal(run(top, child, fl), fl["exp"])
+    assert build_counters(top)["sources"] > 0 and build_counters(child)["sources"] > 0
+    snaps = [top.stats(), child.stats()]
+    assert_impact_equal(run(top, child, fl), fl["exp"])
+    assert [top.stats(), child.stats()] == snaps  # the second call built nothing
+    assert_table_equal(top, c["t0"])
+    assert_table_equal(child, c["t1"])
+
+
+def test_impact_rebuilds_stale_tables_with_equal_attached_sets():
+    c, fl = case("real"), impact_flows("real")
+    top = product("real")
+    child = top.without(edges=c["fail"])
+    assert_impact_equal(run(top, child, fl), fl["exp"])
+    before = [build_counters(top), build_counters(child)]
+    extra = host_ip(5000)
+    v = attach_off_column(c, top, child, ip=extra)
+    A = len(c["t0"][0]) + 1
+    # both tables are stale, the attached sets equal: neither -4 nor -5 (flow_impact raises on a
+    # negative return), the impact between the tables of the new set; the new host sends and
+    # receives one flow
+    s = np.append(fl["src_ip"], [extra, fl["src_ip"][1]]).astype(np.uint32)
+    d = np.append(fl["dst_ip"], [fl["dst_ip"][1], extra]).astype(np.uint32)
+    w = np.append(fl["weight"], [3, 2**63 + 5]).astype(np.uint64)
+    got = top.flow_impact(child, s, d, weight=w, rise_edges_ns=fl["edges"])
+    after = [build_counters(top), build_counters(child)]
+    for b, a in zip(before, after):
+        assert a["paths_computed"] > b["paths_computed"] and a["targets"] == A
+    t0, t1 = top.table(), child.table()  # (the snapshots afterwards: they rebuild nothing)
+    assert [build_counters(top), build_counters(child)] == after
+    assert len(t0[0]) == A and v in t0[0]
+    moved = dict(c, ips=c["ips"] + (extra,), verts=c["verts"] + (v,))
+    sc, dc = columns_of(moved, s, t0[0]), columns_of(moved, d, t0[0])
+    assert sc[-2] >= 0 and dc[-1] >= 0 and (sc < 0).sum() + (dc < 0).sum() == 5
+    exp = expected_impact(t0, t1, sc, dc, w, fl["edges"])
+    assert exp["total"] >= fl["exp"]["total"]
+    assert_impact_equal(got, exp)
+    # the device variant: the host leaves again, both tables are stale once more
+    top.detach_ip(extra), child.detach_ip(extra)
+    before = [build_counters(top), build_counters(child)]
+    dev = top.flow_impact_device(child, cu(fl["src_col"]), cu(fl["dst_col"]),
+                                 rise_edges_ns=fl["edges"])
+    for b, t in zip(before, (top, child)):
+        assert build_counters(t)["paths_computed"] > b["paths_computed"]
+    assert_table_equal(top, c["t0"])
+    assert_table_equal(child, c["t1"])
+    assert_impact_equal(dev, expected_impact(c["t0"], c["t1"], fl["src_col"], fl["dst_col"], None,
+                                             fl["edges"]))
+
+
+def test_same_topology_builds_no_table():
+    """a is b: nothing can change, and the impact -- unlike the diff, which still demands a current
+    table (test_whatif.test_diff_with_itself_builds_the_table) -- counts on the host."""
+    fl = impact_flows("real")
+    want = fl["exp"]["totals"]
+    n = want["flows"]
+    top = product("real")
+    got = run(top, top, fl)
+    tt = got["totals"]
+    assert got["total"] == 0 and len(got["records"]) == 0
+    assert (tt["flows"], tt["compared"], tt["unattached"]) == (n, want["compared"], 5)
+    assert tt["weight"] == want["weight"] and tt["changed"] == 0 and tt["worstFlow"] == -1
+    for k in ("rise_count", "rise_weight", "src_changed_weight", "dst_changed_weight"):
+        assert not got[k].any(), k
+    st = top.flow_impact_stats()
+    assert st["flows"] == n and st["changed"] == 0 and st["kernel_ms"] == 0
+    assert st["words_skipped"] == (n + 63) // 64
+    pay = np.random.default_rng(43).integers(0, 2**32, n, dtype=np.uint32)
+    ok = (fl["src_col"] >= 0) & (fl["dst_col"] >= 0)
+    for payload, weight in ((pay, usum(pay[ok])), (None, int(ok.sum()))):
+        dev = top.flow_impact_device(top, cu(fl["src_col"]), cu(fl["dst_col"]),
+                                     payload=None if payload is None else cu(payload),
+                                     rise_edges_ns=fl["edges"])
+        tt = dev["totals"]
+        assert dev["total"] == 0 and tt["changed"] == 0
+        assert (tt["flows"], tt["compared"], tt["unattached"]) == (n, int(ok.sum()), 5)
+        assert tt["weight"] == weight
+    built = build_counters(top)
+    assert built["paths_computed"] == 0 and built["sources"] == 0 and built["build_ms"] == 0

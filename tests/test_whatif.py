@@ -13,8 +13,9 @@ import pytest
 import shadow_amd as sa
 from helpers import host_ip
 from shadow_amd import _lib
-from whatif_helpers import (CHANGE, FELL, ROSE, assert_diff_equal, assert_table_equal, case,
-                            expected_diff, filtered, product, swapped)
+from whatif_helpers import (CHANGE, FELL, ROSE, assert_diff_equal, assert_table_equal,
+                            attach_off_column, build_counters, case, expected_diff, filtered,
+                            product, swapped)
 
 pytestmark = pytest.mark.gpu
 
@@ -211,3 +212,84 @@ def test_errors_and_side_effects():
     with pytest.raises(RuntimeError) as e:
         top.table_diff(child)
     assert e.value.args[1] == -4
+
+
+# ---- the paths of the pair loop (with_current_pair, topo_whatif.cpp) the tests above do not reach:
+# ---- they build both tables first
+
+def test_diff_builds_missing_tables():
+    c = case("real")
+    top = product("real")
+    child = top.without(edges=c["fail"])
+    # no build and no getter so far: the call builds both tables
+    assert_diff_equal(top.table_diff(child), c["exp"])
+    assert build_counters(top)["sources"] > 0 and build_counters(child)["sources"] > 0
+    snaps = [top.stats(), child.stats()]
+    assert_diff_equal(top.table_diff(child), c["exp"])
+    assert [top.stats(), child.stats()] == snaps  # the second call built nothing
+    assert_table_equal(top, c["t0"])
+    assert_table_equal(child, c["t1"])
+
+
+def test_diff_rebuilds_stale_tables_with_equal_attached_sets():
+    c = case("real")
+    top = product("real")
+    child = top.without(edges=c["fail"])
+    assert_diff_equal(top.table_diff(child), c["exp"])
+    before = [build_counters(top), build_counters(child)]
+    v = attach_off_column(c, top, child)
+    A = len(c["t0"][0]) + 1
+    assert len(top.attached_vertices()) == A and v in top.attached_vertices()
+    # both tables are stale, the attached sets equal: neither -4 nor -5 (table_diff raises on a
+    # negative return), the diff of the tables of the new set
+    got = top.table_diff(child)
+    after = [build_counters(top), build_counters(child)]
+    for b, a in zip(before, after):
+        assert a["paths_computed"] > b["paths_computed"] and a["targets"] == A
+    t0, t1 = top.table(), child.table()  # (the snapshots afterwards: they rebuild nothing)
+    assert [build_counters(top), build_counters(child)] == after
+    assert len(t0[0]) == A
+    assert got["total"] >= c["exp"]["total"] and len(got["row_changed"]) == A
+    assert_diff_equal(got, expected_diff(t0, t1))
+
+
+def test_diff_with_itself_builds_the_table():
+    """a is b: nothing can differ, but the diff still demands a current table (the flow impact
+    does not: test_flow_impact.test_same_topology_builds_no_table)."""
+    c = case("real")
+    top = product("real")
+    A = len(c["t0"][0])
+    assert build_counters(top)["paths_computed"] == 0
+    got = top.table_diff(top)
+    assert got["total"] == 0 and len(got["records"]) == 0 and not got["kind_count"].any()
+    assert len(got["row_changed"]) == A and not got["row_changed"].any()
+    assert len(got["row_worst_rise"]) == A and not got["row_worst_rise"].any()
+    assert len(got["row_worst_col"]) == A and (got["row_worst_col"] == -1).all()
+    st = top.table_diff_stats()
+    assert st["pairs"] == A * A and st["changed"] == 0
+    built = build_counters(top)
+    assert built["paths_computed"] == A and built["targets"] == A
+    # it left a current table behind
+    lat, rel = np.empty((A, A), np.float64), np.empty((A, A), np.float64)
+    hops = np.empty((A, A), np.uint16)
+    lib, _ = _lib.load()
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    assert lib.shdtopo_table_to_host(top._h, p(lat), p(rel), p(hops)) == 0
+    assert build_counters(top) == built
+    assert np.array_equal(lat.view(np.uint64), c["t0"][1].view(np.uint64))
+    assert_table_equal(top, c["t0"])
+    assert build_counters(top) == built
+
+
+def test_diff_stats_stay_with_the_first_argument():
+    c = case("real")
+    top = product("real")
+    child = top.without(edges=c["fail"])
+    child.table_diff(top, cap=0)
+    mine = child.table_diff_stats()
+    assert mine["pairs"] == len(c["t0"][0]) ** 2 and mine["changed"] == c["exp"]["total"]
+    fresh = top.table_diff_stats()
+    assert fresh["pairs"] == 0 and fresh["changed"] == 0
+    top.table_diff(child)
+    assert child.table_diff_stats() == mine  # written to the first argument only
+    assert top.table_diff_stats()["changed"] == c["exp"]["total"]

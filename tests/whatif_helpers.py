@@ -235,3 +235,28 @@ def assert_table_equal(top, t):
     assert np.array_equal(lat.view(np.uint64), olat.view(np.uint64))
     assert np.array_equal(rel.view(np.uint64), orel.view(np.uint64))
     assert np.array_equal(hops, ohops.astype(np.uint16))
+
+
+def attach_off_column(c, parent, child, ip=host_ip(5000), state=12345):
+    """One more host on parent and child, on the same vertex, one that is no column of case c yet;
+    returns the vertex.  The bundled graphs give their vertices no ip, so no ipHint can pin it:
+    the host's random stream does (the same state draws the same candidate on both), and the state
+    is the first one of the stream that lands off the columns."""
+    while True:
+        v, nxt = parent.attach_ip(ip, state)
+        if v not in c["verts"]:
+            break
+        parent.detach_ip(ip)
+        state = nxt
+    assert child.attach_ip(ip, state)[0] == v
+    assert np.array_equal(parent.attached_vertices(), child.attached_vertices())
+    return v
+
+
+BUILD_COUNTERS = ("paths_computed", "sources", "targets", "build_ms")
+
+
+def build_counters(top):
+    """The fields of stats() a table build moves."""
+    st = top.stats()
+    return {k: st[k] for k in BUILD_COUNTERS}
