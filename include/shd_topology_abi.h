@@ -1050,6 +1050,94 @@ int64_t shdtopo_flow_impact_device(Topology* a, Topology* b, const int32_t* d_sr
                                    uint64_t* dstChangedWeight, void* stream);
 int shdtopo_flow_impact_stats(Topology* a, ShdImpactStats* out);
 
+/* ---- load shift: where a link failure moves a set of flows' traffic ----
+ * shdtopo_flow_impact answers "which of my flows change"; shdtopo_load_shift answers where their
+ * traffic goes: n flows (source host, destination host, weight -- the inputs of shdtopo_link_load)
+ * are accumulated on a and on b, each by that topology's own load path and options ("load_walk",
+ * "trace_batch", "trace_chunk"), both results stay on the device, are brought into the root
+ * topology's numbering -- the numbering of shdtopo_edge_origin -- and compared entry by entry
+ * there.  Only the entries whose load differs, and integer totals, leave the device.
+ *
+ * Index space.  R = the root's edge count, V = the vertex count.  Entry x in [0, 2 R + V) is
+ *   x < R         the forward half of root edge x       (edgeLoad[e] of shdtopo_link_load),
+ *   R <= x < 2 R  the reverse half of root edge x - R   (edgeLoad[E + e]),
+ *   x >= 2 R      vertex x - 2 R                        (vertexLoad).
+ * before(x) is a's load and after(x) is b's; an edge a topology lacks carries 0 there.  An entry
+ * is changed exactly when before != after, compared as u64: a failed edge that carried nothing is
+ * not reported.  Returns the number of changed entries; out receives the first min(total, cap)
+ * records in ascending x (cap = 0 with out = NULL sizes the buffer), nothing at or beyond cap is
+ * touched, and totals (may be NULL) is complete whatever cap is.
+ *
+ * Sums are u64 and wrap, comparisons are unsigned, there is no float anywhere: no output depends
+ * on flow order, chunking, tiling or scheduling.
+ *
+ * Flows are resolved once, through a's map, as shdtopo_flow_impact does (vertex ids are common to
+ * both topologies).  a and b may be parent and child, child and parent, two siblings, a topology
+ * and a derivation of a derivation, or two loads of one file: beyond the checks below, edge
+ * identity is the caller's word, as column identity is for shdtopo_table_diff.  Errors: -1 bad
+ * arguments (a NULL topology, n < 0 or n > 2^31 - 2, a NULL IP array with n > 0, cap < 0, NULL out
+ * with cap > 0); -7 the vertex counts or the root edge counts differ; -4 the attached vertex lists
+ * differ; -6 the two topologies run their loads on different devices.  Argument errors, -7 and -4
+ * are returned before any device is used.  Both build locks are taken, the lower address first,
+ * for the whole call.  No table is needed, built or invalidated; like shdtopo_link_load the call
+ * materialises no lazy row, pushes no minimum and leaves ShdStats and every other statistic of the
+ * family -- both topologies' ShdLoadStats included -- exactly as it was.  a == b is valid: one
+ * accumulation serves both sides and the call returns 0 with the totals of that load.  A complete
+ * topology is accumulated on the host as shdtopo_link_load does and its sums are uploaded; when
+ * both sides are complete the whole answer is computed on the host and no device is used.
+ *
+ * Device work (topo_shift.hip).  Each side brings the ascending list of the root edge ids it lacks
+ * (a handful after a link failure; nothing for a root topology), and its own id of root edge r is
+ * r - (the listed ids below r).  A count pass over tiles of 256 x U entries (tile_entries of the
+ * statistics) loads both sides, keeps one ballot word per 64 entries, reduces the totals in
+ * registers and LDS and numbers the tiles' changed entries; one workgroup merges the tiles'
+ * {largest, lowest x} pairs; an exclusive scan places the tiles; a fill pass loads again only for
+ * the words that have a changed entry below cap and writes the 32-B records at their ranks:
+ * ascending x with no sort and no atomic.  shdtopo_load_shift_stats reads the statistics of the
+ * last call in which `a` was the first argument.  bytes_model: the count pass reads 8 B per side
+ * and entry the side has and writes one 8-B word per 64 entries and 72 B per tile; the fill pass
+ * reads 16 B and writes 32 B for every record it writes. */
+typedef struct {            /* 32 B: two 16-B stores on the device */
+    int32_t  kind;          /* 0 forward half, 1 reverse half, 2 vertex */
+    int32_t  id;            /* root edge id, or vertex id */
+    int32_t  idA, idB;      /* the edge's id in a / in b, -1: that topology lacks it; vertices: id */
+    uint64_t before, after;
+} ShdLoadChange;
+
+typedef struct {
+    int64_t  flows, unattached;
+    int64_t  routedA, routedB, brokenA, brokenB;
+    uint64_t hopWeightA, hopWeightB;             /* link_load's hop_weight on each side */
+    int64_t  changed[3], gained[3], lost[3];     /* entries by kind; gained: after > before */
+    int64_t  newlyUsed[3], abandoned[3];         /* before == 0 < after / after == 0 < before */
+    uint64_t gainedWeight[3], lostWeight[3];     /* wrapping sums of after-before / before-after */
+    uint64_t displaced, appeared;                /* sum of before over edge halves b lacks / of after over halves a lacks */
+    uint64_t worstGain, worstLoss;               /* largest after-before / before-after; 0 if none */
+    int64_t  worstGainIndex, worstLossIndex;     /* the lowest x reaching it; -1 if none */
+    uint64_t peakBefore, peakAfter;              /* largest load over the edge halves (x < 2R) */
+    int64_t  peakBeforeIndex, peakAfterIndex;    /* lowest x reaching it; -1 when all are 0 */
+} ShdShiftTotals;
+
+typedef struct {
+    double  total_ms;       /* wall time of the call */
+    double  resolve_ms;     /* of it: resolving the IPs to vertices on the host */
+    double  load_a_ms;      /* of it: a's accumulation, wall time (a complete side: its upload included) */
+    double  load_b_ms;      /* of it: b's (0 when a == b) */
+    double  kernel_ms;      /* event time of the compare kernels only: count, reduce, scan, fill */
+    int64_t entries;        /* 2 R + V */
+    int64_t changed;        /* the call's return value */
+    int64_t words_skipped;  /* 64-entry words (of (entries + 63) / 64) the fill pass did not load for */
+    int64_t bytes_model;    /* the byte model above, summed over the call (0: answered on the host) */
+    int64_t tile_entries;   /* entries per workgroup of this build: 256 x U */
+    ShdLoadStats loadA, loadB;  /* each side's accumulation as shdtopo_link_load_stats would report
+                                   it (total_ms: the side's wall time; loadB = loadA when a == b) */
+} ShdShiftStats;
+
+int64_t shdtopo_load_shift(Topology* a, Topology* b, const uint32_t* srcIP, const uint32_t* dstIP,
+                           const uint64_t* weight /* NULL: 1 each */, int64_t n,
+                           ShdLoadChange* out, int64_t cap, ShdShiftTotals* totals);
+int shdtopo_load_shift_stats(Topology* a, ShdShiftStats* out);
+
 /* Test hook: the device graph preparation (topo_prep.hip) read back -- perm
  * int32[V] (relabelled -> original vertex), rowptr u32[V+1], the adjacency columns u32[2E']
  * (relabelled ids, rows ascending by neighbour), pi f64[V] (= d(h0, .), relabelled ids) and the

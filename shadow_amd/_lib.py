@@ -144,6 +144,29 @@ class ShdImpactStats(ctypes.Structure):
                 ("tile_flows", i64)]
 
 
+class ShdLoadChange(ctypes.Structure):
+    _fields_ = [("kind", i32), ("id", i32), ("idA", i32), ("idB", i32), ("before", u64),
+                ("after", u64)]
+
+
+class ShdShiftTotals(ctypes.Structure):
+    _fields_ = [("flows", i64), ("unattached", i64), ("routedA", i64), ("routedB", i64),
+                ("brokenA", i64), ("brokenB", i64), ("hopWeightA", u64), ("hopWeightB", u64),
+                ("changed", i64 * 3), ("gained", i64 * 3), ("lost", i64 * 3),
+                ("newlyUsed", i64 * 3), ("abandoned", i64 * 3), ("gainedWeight", u64 * 3),
+                ("lostWeight", u64 * 3), ("displaced", u64), ("appeared", u64),
+                ("worstGain", u64), ("worstLoss", u64), ("worstGainIndex", i64),
+                ("worstLossIndex", i64), ("peakBefore", u64), ("peakAfter", u64),
+                ("peakBeforeIndex", i64), ("peakAfterIndex", i64)]
+
+
+class ShdShiftStats(ctypes.Structure):
+    _fields_ = [("total_ms", dbl), ("resolve_ms", dbl), ("load_a_ms", dbl), ("load_b_ms", dbl),
+                ("kernel_ms", dbl), ("entries", i64), ("changed", i64), ("words_skipped", i64),
+                ("bytes_model", i64), ("tile_entries", i64), ("loadA", ShdLoadStats),
+                ("loadB", ShdLoadStats)]
+
+
 class ShdSynthParams(ctypes.Structure):
     _fields_ = [("seed", u64), ("n_routers", i64), ("n_poi", i64), ("n_edges", i64),
                 ("integer_latency", ctypes.c_int), ("alpha", dbl), ("directed", ctypes.c_int)]
@@ -221,6 +244,8 @@ SIGNATURES = {
     "shdtopo_flow_impact": (i64, [P, P, P, P, P, i64, P, i64, P, i64, P, P, P, P, P]),
     "shdtopo_flow_impact_device": (i64, [P, P, P, P, P, i64, P, i64, P, i64, P, P, P, P, P, P]),
     "shdtopo_flow_impact_stats": (ctypes.c_int, [P, P]),
+    "shdtopo_load_shift": (i64, [P, P, P, P, P, i64, P, i64, P]),
+    "shdtopo_load_shift_stats": (ctypes.c_int, [P, P]),
     "shdtopo_test_segsort": (ctypes.c_int, [P, i64, P, i64, ctypes.c_int, P, P]),
     "shdtopo_test_batch_layout": (ctypes.c_int, [P, i64, dbl, ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_int, P, P, P]),

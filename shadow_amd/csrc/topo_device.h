@@ -711,6 +711,60 @@ hipError_t launch_impact_fill(const DiffTables& t, const ImpactFlows& f,
                               const int64_t* tileOff, ImpactRec* out, int64_t cap,
                               unsigned long long* gathered, hipStream_t stream);
 
+// ---- load shift (topo_shift.hip): the entries whose load differs between two link loads ----
+// one changed entry: the device image of ShdLoadChange (include/shd_topology_abi.h)
+struct __attribute__((aligned(16))) ShiftRec {
+    int32_t kind, id, idA, idB;
+    unsigned long long before, after;
+};
+// the u64 totals of one call (zeroed by the caller): five counts and two weighted sums by kind
+// (forward half, reverse half, vertex), then the two sums over the halves one side lacks
+enum {
+    SH_CHANGED = 0, SH_GAINED = 3, SH_LOST = 6, SH_NEW = 9, SH_ABANDONED = 12, SH_GAINED_W = 15,
+    SH_LOST_W = 18, SH_DISPLACED = 21, SH_APPEARED, SH_COUNT
+};
+// the {largest value, lowest entry reaching it} pairs of one call
+enum { SP_GAIN = 0, SP_LOSS, SP_PEAK_BEFORE, SP_PEAK_AFTER, SP_COUNT };
+// One side of the comparison: a link load's sums on the device -- eload u64 [2 E] by the side's own
+// edge ids (forward halves, then reverse halves), vload u64 [V] by original vertex id -- and its
+// place in the root's numbering: gaps = the root edge ids the side lacks, strictly ascending,
+// ngaps = R - E of them (none: a root topology).  Root edge r is the side's edge r - (the number
+// of gaps below r), or no edge of it when r is a gap.
+struct ShiftSide {
+    const unsigned long long* eload = nullptr;
+    const unsigned long long* vload = nullptr;
+    const int32_t* gaps = nullptr;
+    int32_t ngaps = 0;
+    int64_t E = 0;
+};
+// The entries x in [0, 2 R + V) of one call -- forward halves, reverse halves, vertices -- and what
+// the count pass writes.  Tile blk = entries [blk T, (blk + 1) T), T = shift_tile_entries(); words
+// has T / 64 words per tile (every word of every tile is written); tileChanged has one entry per
+// tile; tileVal / tileIdx have SP_COUNT per tile: the tile's pairs (0 / -1: none).
+struct ShiftIn {
+    ShiftSide a, b;
+    int64_t R = 0, V = 0;
+};
+struct ShiftOut {
+    unsigned long long* words = nullptr;
+    int64_t* tileChanged = nullptr;
+    unsigned long long* tileVal = nullptr;
+    int64_t* tileIdx = nullptr;
+    unsigned long long* tot = nullptr;
+};
+int64_t shift_tile_entries();
+hipError_t launch_shift_count(const ShiftIn& in, const ShiftOut& o, hipStream_t stream);
+// the call's pairs from the tiles': pairVal u64 [SP_COUNT], pairIdx i64 [SP_COUNT]
+hipError_t launch_shift_reduce(int64_t tiles, const unsigned long long* tileVal,
+                               const int64_t* tileIdx, unsigned long long* pairVal,
+                               int64_t* pairIdx, hipStream_t stream);
+// Fill: the changed entries' records at out[tileOff[blk] + rank in the tile] (tileOff: the
+// exclusive scan of tileChanged); records at or past cap are not written.  gathered: as
+// launch_impact_fill's.
+hipError_t launch_shift_fill(const ShiftIn& in, const unsigned long long* words,
+                             const int64_t* tileChanged, const int64_t* tileOff, ShiftRec* out,
+                             int64_t cap, unsigned long long* gathered, hipStream_t stream);
+
 hipError_t launch_pair_table_complete(int A, int64_t row0, int64_t rows, const double* elatAA,
                                       const double* elossAA, const double* vlossA, double2* out_lr,
                                       uint16_t* out_hops, double* out_rowmin,

@@ -578,17 +578,20 @@ int64_t load_complete(Topology* top, const std::vector<int32_t>& sv, const std::
 }
 
 // SSSP topologies: the distinct sources in chunks -- chains from the batch kernel's pair records
-// (the per-request walk only) or the replay (chunk_chains) -- and the sums along the chains
-int64_t load_replay(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
-                    const uint64_t* weight, int64_t n, uint64_t* edgeLoad, uint64_t* vertexLoad,
-                    ShdLoadStats* ls, ChainStats& cs) {
+// (the per-request walk only) or the replay (chunk_chains) -- and the sums along the chains, left
+// on the device in the caller's holder (topo_host.h)
+int load_accumulate(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
+                    const uint64_t* weight, int64_t n, LoadSums& sums, ShdLoadStats* ls,
+                    ChainStats& cs) {
     ReplayReqs R;
     CHK(group_replay_requests(top, sv, dv, n, &cs.ids_ms, !top->loadWalk, R));
     hipStream_t st = top->stream;
     const size_t V = (size_t)top->g.V, E = (size_t)top->g.E;
 
     Walk wk;
-    DevBuf<unsigned long long> d_eload, d_vload, d_vout;
+    DevBuf<unsigned long long>& d_eload = sums.d_eload;
+    DevBuf<unsigned long long>& d_vout = sums.d_vout;
+    DevBuf<unsigned long long> d_vload;  // by relabelled vertex: permuted into d_vout below
     HIPCHK(d_eload.ensure(2 * E));
     HIPCHK(d_vload.ensure(V));
     HIPCHK(d_vout.ensure(V));
@@ -621,8 +624,6 @@ int64_t load_replay(Topology* top, const std::vector<int32_t>& sv, const std::ve
     HIPCHK(launch_load_permute((int64_t)V, R.ids.perm, d_vload.p, d_vout.p, st));
     HIPCHK(hipEventRecord(R.ev.e[1], st));
     HIPCHK(hipMemcpyAsync(wk.cnt, wk.d_cnt.p, 8 * LD_COUNT, hipMemcpyDeviceToHost, st));
-    if (edgeLoad && E) HIPCHK(hipMemcpyAsync(edgeLoad, d_eload.p, 8 * 2 * E, hipMemcpyDeviceToHost, st));
-    if (vertexLoad && V) HIPCHK(hipMemcpyAsync(vertexLoad, d_vout.p, 8 * V, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipEventElapsedTime(&ms, R.ev.e[0], R.ev.e[1]));
     cs.kernel_ms += ms;
@@ -630,7 +631,19 @@ int64_t load_replay(Topology* top, const std::vector<int32_t>& sv, const std::ve
     ls->broken = wk.broken();
     ls->hop_weight = wk.total(LD_HOPW);
     ls->tree_vertices = (int64_t)wk.total(LD_TREE);
-    return ls->routed;
+    return 0;
+}
+
+// the copy-out of a link load: the accumulated sums to the caller's arrays
+int load_copy_out(Topology* top, const LoadSums& sums, uint64_t* edgeLoad, uint64_t* vertexLoad) {
+    hipStream_t st = top->stream;
+    const size_t V = (size_t)top->g.V, E = (size_t)top->g.E;
+    if (edgeLoad && E)
+        HIPCHK(hipMemcpyAsync(edgeLoad, sums.d_eload.p, 8 * 2 * E, hipMemcpyDeviceToHost, st));
+    if (vertexLoad && V)
+        HIPCHK(hipMemcpyAsync(vertexLoad, sums.d_vout.p, 8 * V, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1027,7 +1040,12 @@ int64_t shdtopo_link_load(Topology* top, const uint32_t* srcIP, const uint32_t* 
     ls.unattached = n - nvalid;
     int64_t routed = 0;
     if (top->isComplete) routed = load_complete(top, sv, dv, weight, n, edgeLoad, vertexLoad, &ls);
-    else if (nvalid > 0) routed = load_replay(top, sv, dv, weight, n, edgeLoad, vertexLoad, &ls, cs);
+    else if (nvalid > 0) {  // the accumulation, then the copy-out
+        LoadSums sums;
+        int r = load_accumulate(top, sv, dv, weight, n, sums, &ls, cs);
+        if (!r) r = load_copy_out(top, sums, edgeLoad, vertexLoad);
+        routed = r ? r : ls.routed;
+    }
     cs.out(&ls, &ShdLoadStats::load_kernel_ms);
     ls.ids_ms = cs.ids_ms;
     ls.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

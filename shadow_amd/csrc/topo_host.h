@@ -146,8 +146,10 @@ struct _Topology {
     std::vector<int32_t> edgeOrigin;
     std::vector<uint8_t> failedVertex;
     bool preChecked = false;
+    int64_t rootE = -1;  // a derived topology: the root's edge count, inherited (-1: a root, g.E)
     ShdDiffStats diffStats{};  // table diff (shdtopo_table_diff, topo_diff.hip): first argument's
     ShdImpactStats impactStats{};  // flow impact (shdtopo_flow_impact, topo_impact.hip): likewise
+    ShdShiftStats shiftStats{};    // load shift (shdtopo_load_shift, topo_shift.hip): likewise
 
     // options ("abort_on_error" and "lazy" are read by getters on worker threads without a lock)
     std::atomic<bool> abortOnError{true};
@@ -779,5 +781,25 @@ struct Walk {
     int64_t routed() const { return (int64_t)total(LD_ROUTED); }
     int64_t broken() const { return (int64_t)total(LD_BROKEN); }
 };
+
+// A link load's sums on the device, caller-owned: d_eload u64 [2 E] by document edge id (the
+// forward halves, then the reverse halves), d_vout u64 [V] by original vertex id.
+struct LoadSums {
+    DevBuf<unsigned long long> d_eload, d_vout;
+};
+// The link load of an SSSP topology in two steps (shdtopo_link_load runs both; the load shift of
+// topo_whatif.cpp runs the first on each side and compares on the device).  load_accumulate: the
+// sums of the requests (sv / dv: their vertices, -1 = not attached) into `sums`, complete when it
+// returns (the stream is synchronised), and routed / broken / hop_weight / tree_vertices into ls.
+// load_copy_out: the sums to the host arrays (either may be NULL).  Each holds buildMu.
+int load_accumulate(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
+                    const uint64_t* weight, int64_t n, LoadSums& sums, ShdLoadStats* ls,
+                    ChainStats& cs);
+int load_copy_out(Topology* top, const LoadSums& sums, uint64_t* edgeLoad, uint64_t* vertexLoad);
+// a complete topology's link load, on the host from the parsed graph (adds into edgeLoad u64
+// [2 E] / vertexLoad u64 [V], either may be NULL; routed / broken / hop_weight into ls)
+int64_t load_complete(Topology* top, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
+                      const uint64_t* weight, int64_t n, uint64_t* edgeLoad, uint64_t* vertexLoad,
+                      ShdLoadStats* ls);
 
 }  // namespace shdtopo

@@ -1,9 +1,11 @@
 // topo_whatif.cpp -- the link failure what-if family behind the C ABI of
 // include/shd_topology_abi.h: derived topologies (shdtopo_derive_without, shdtopo_edge_origin), the
-// table diff (shdtopo_table_diff*; kernels in topo_diff.hip) and the flow impact
-// (shdtopo_flow_impact*; kernels in topo_impact.hip).  The diff and the impact compare the resident
-// tables of two topologies: one driver, with_current_pair, takes their locks and brings the tables
-// up to date for both.
+// table diff (shdtopo_table_diff*; kernels in topo_diff.hip), the flow impact
+// (shdtopo_flow_impact*; kernels in topo_impact.hip) and the load shift (shdtopo_load_shift*;
+// kernels in topo_shift.hip).  The diff and the impact compare the resident tables of two
+// topologies: one driver, with_current_pair, takes their locks and brings the tables up to date
+// for both.  The shift needs no table: it takes both locks itself, runs the link load's
+// accumulation (topo_flows.cpp) on each side and compares the two results where they are.
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
@@ -390,6 +392,345 @@ int64_t flow_impact(Topology* a, Topology* b, const ImpactCall& c) {
     });
 }
 
+// ---- load shift (shdtopo_load_shift; kernels in topo_shift.hip) ----
+
+static_assert(sizeof(ShdLoadChange) == 32 && sizeof(ShiftRec) == sizeof(ShdLoadChange) &&
+                  offsetof(ShdLoadChange, idA) == offsetof(ShiftRec, idA) &&
+                  offsetof(ShdLoadChange, before) == 16 && offsetof(ShiftRec, before) == 16,
+              "ShiftRec is the device image of ShdLoadChange");
+
+int64_t root_edges(const Topology* t) { return t->rootE >= 0 ? t->rootE : t->g.E; }
+
+// The root edge ids t lacks, ascending: the complement of its origins in [0, R).  false: the
+// origins are not E strictly ascending ids of [0, R) (so the gaps are R - E distinct ids, which is
+// what bounds the kernels' loads).
+bool root_gaps(const Topology* t, int64_t R, std::vector<int32_t>& gaps) {
+    gaps.clear();
+    const int64_t E = t->g.E;
+    if (t->edgeOrigin.empty()) return E == R;
+    if ((int64_t)t->edgeOrigin.size() != E || E > R) return false;
+    int64_t next = 0;
+    for (int64_t e = 0; e < E; e++) {
+        const int64_t r = t->edgeOrigin[(size_t)e];
+        if (r < next || r >= R) return false;
+        for (; next < r; next++) gaps.push_back((int32_t)next);
+        next = r + 1;
+    }
+    for (; next < R; next++) gaps.push_back((int32_t)next);
+    return true;
+}
+
+// one side of a shift: the load of the call's flows on one topology
+struct ShiftLoad {
+    Topology* top = nullptr;
+    std::vector<int32_t> gaps;
+    bool onHost = false;               // a complete topology: accumulated on the host
+    std::vector<uint64_t> eload, vload;  // ... into these (u64 [2 E], u64 [V])
+    LoadSums dev;                      // the sums on the device (a host side's upload)
+    ShdLoadStats ls{};
+    double ms = 0.0;
+    // the host image of kernel's side_id: the side's id of root edge r, -1: it lacks it
+    int32_t id_of(int32_t r) const {
+        const auto it = std::lower_bound(gaps.begin(), gaps.end(), r);
+        if (it != gaps.end() && *it == r) return -1;
+        return r - (int32_t)(it - gaps.begin());
+    }
+};
+
+// the accumulation of one side as shdtopo_link_load runs it, its statistics into s.ls
+int shift_accumulate(ShiftLoad& s, const std::vector<int32_t>& sv, const std::vector<int32_t>& dv,
+                     const uint64_t* weight, int64_t n, int64_t nvalid) {
+    const auto t0 = std::chrono::steady_clock::now();
+    Topology* top = s.top;
+    ChainStats cs;
+    s.ls = ShdLoadStats{};
+    s.ls.requests = n;
+    s.ls.unattached = n - nvalid;
+    int r = 0;
+    if (top->isComplete) {
+        s.onHost = true;
+        s.eload.assign(2 * (size_t)top->g.E, 0);
+        s.vload.assign((size_t)top->g.V, 0);
+        load_complete(top, sv, dv, weight, n, s.eload.data(), s.vload.data(), &s.ls);
+    } else {
+        r = load_accumulate(top, sv, dv, weight, n, s.dev, &s.ls, cs);
+    }
+    cs.out(&s.ls, &ShdLoadStats::load_kernel_ms);
+    s.ls.ids_ms = cs.ids_ms;
+    s.ls.total_ms = s.ms = ms_since(t0);
+    return r;
+}
+
+// a host side's sums to the device (the other side is not complete); the device is bound
+int shift_upload(ShiftLoad& s) {
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(s.dev.d_eload.ensure(s.eload.size()));
+    HIPCHK(s.dev.d_vout.ensure(s.vload.size()));
+    if (!s.eload.empty())
+        HIPCHK(hipMemcpy(s.dev.d_eload.p, s.eload.data(), 8 * s.eload.size(), hipMemcpyHostToDevice));
+    if (!s.vload.empty())
+        HIPCHK(hipMemcpy(s.dev.d_vout.p, s.vload.data(), 8 * s.vload.size(), hipMemcpyHostToDevice));
+    s.ms += ms_since(t0);
+    s.ls.total_ms = s.ms;
+    return 0;
+}
+
+// what one changed or unchanged entry adds to the totals (the host image of shift_count_kernel)
+struct ShiftFold {
+    ShdShiftTotals* tt;
+    void peak(int64_t x, uint64_t before, uint64_t after) const {
+        if (before > tt->peakBefore) {  // ascending x: the first to reach the maximum stays
+            tt->peakBefore = before;
+            tt->peakBeforeIndex = x;
+        }
+        if (after > tt->peakAfter) {
+            tt->peakAfter = after;
+            tt->peakAfterIndex = x;
+        }
+    }
+    void change(int64_t x, const ShdLoadChange& c) const {
+        const int k = c.kind;
+        tt->changed[k]++;
+        if (c.after > c.before) {
+            const uint64_t d = c.after - c.before;
+            tt->gained[k]++;
+            tt->gainedWeight[k] += d;
+            if (c.before == 0) tt->newlyUsed[k]++;
+            if (d > tt->worstGain) {
+                tt->worstGain = d;
+                tt->worstGainIndex = x;
+            }
+        } else {
+            const uint64_t d = c.before - c.after;
+            tt->lost[k]++;
+            tt->lostWeight[k] += d;
+            if (c.after == 0) tt->abandoned[k]++;
+            if (d > tt->worstLoss) {
+                tt->worstLoss = d;
+                tt->worstLossIndex = x;
+            }
+        }
+        if (k < 2 && c.idB < 0) tt->displaced += c.before;
+        if (k < 2 && c.idA < 0) tt->appeared += c.after;
+    }
+};
+
+// both sides on the host (two complete topologies): the whole answer without a device
+int64_t shift_on_host(const ShiftLoad& sa, const ShiftLoad& sb, int64_t R, int64_t V,
+                      ShdLoadChange* out, int64_t cap, ShdShiftTotals* tt) {
+    const ShiftFold fold{tt};
+    const int64_t Ea = sa.top->g.E, Eb = sb.top->g.E;
+    int64_t total = 0;
+    for (int64_t x = 0; x < 2 * R + V; x++) {
+        ShdLoadChange c;
+        if (x >= 2 * R) {
+            c.kind = 2;
+            c.id = c.idA = c.idB = (int32_t)(x - 2 * R);
+            c.before = sa.vload[(size_t)c.id];
+            c.after = sb.vload[(size_t)c.id];
+        } else {
+            c.kind = x >= R ? 1 : 0;
+            c.id = (int32_t)(c.kind ? x - R : x);
+            c.idA = sa.id_of(c.id);
+            c.idB = sb.id_of(c.id);
+            c.before = c.idA >= 0 ? sa.eload[(size_t)(c.kind * Ea + c.idA)] : 0;
+            c.after = c.idB >= 0 ? sb.eload[(size_t)(c.kind * Eb + c.idB)] : 0;
+            fold.peak(x, c.before, c.after);
+        }
+        if (c.before == c.after) continue;
+        fold.change(x, c);
+        if (total < cap) out[total] = c;
+        total++;
+    }
+    return total;
+}
+
+// both sides on the device: the compare kernels on a's stream, events of the call's own
+int64_t shift_on_device(Topology* a, const ShiftLoad& sa, const ShiftLoad& sb, int64_t R, int64_t V,
+                        ShdLoadChange* out, int64_t cap, ShdShiftTotals* tt, ShdShiftStats* ss) {
+    hipStream_t st = a->stream;
+    DevBuf<int32_t> d_gapsA, d_gapsB;
+    auto side = [&](const ShiftLoad& s, DevBuf<int32_t>& d_gaps, ShiftSide* o) {
+        const size_t ng = s.gaps.size();
+        if (ng) {
+            HIPCHK(d_gaps.ensure(ng));
+            HIPCHK(hipMemcpy(d_gaps.p, s.gaps.data(), 4 * ng, hipMemcpyHostToDevice));
+        }
+        *o = ShiftSide{s.dev.d_eload.p, s.dev.d_vout.p, ng ? d_gaps.p : nullptr, (int32_t)ng,
+                       s.top->g.E};
+        return 0;
+    };
+    ShiftIn in;
+    in.R = R;
+    in.V = V;
+    CHK(side(sa, d_gapsA, &in.a));
+    if (&sb == &sa) in.b = in.a;
+    else CHK(side(sb, d_gapsB, &in.b));
+
+    const int64_t X = 2 * R + V, T = shift_tile_entries();
+    const int64_t tiles = (X + T - 1) / T, nwords = tiles * (T / 64);
+    DevBuf<unsigned long long> d_words, d_tval, d_tot, d_pval, d_gath;
+    DevBuf<int64_t> d_cnt, d_off, d_tidx, d_pidx;
+    DevBuf<ShiftRec> d_out;
+    HIPCHK(d_words.ensure((size_t)nwords));
+    HIPCHK(d_cnt.ensure((size_t)tiles + 1));
+    HIPCHK(d_off.ensure((size_t)tiles + 1));
+    HIPCHK(d_tval.ensure((size_t)tiles * SP_COUNT));
+    HIPCHK(d_tidx.ensure((size_t)tiles * SP_COUNT));
+    HIPCHK(d_tot.ensure(SH_COUNT));
+    HIPCHK(d_pval.ensure(SP_COUNT));
+    HIPCHK(d_pidx.ensure(SP_COUNT));
+    ShiftOut o;
+    o.words = d_words.p;
+    o.tileChanged = d_cnt.p;
+    o.tileVal = d_tval.p;
+    o.tileIdx = d_tidx.p;
+    o.tot = d_tot.p;
+    HIPCHK(hipMemsetAsync(d_tot.p, 0, 8 * SH_COUNT, st));
+    HIPCHK(hipMemsetAsync(d_cnt.p + tiles, 0, sizeof(int64_t), st));
+    // two event pairs of the call's own: count + reduce + scan, and fill (what the host does in
+    // between -- reading the total, allocating the records -- is not kernel time)
+    DevEvents<4> ev;
+    CHK(ev.create());
+    HIPCHK(hipEventRecord(ev.e[0], st));
+    HIPCHK(launch_shift_count(in, o, st));
+    HIPCHK(launch_shift_reduce(tiles, d_tval.p, d_tidx.p, d_pval.p, d_pidx.p, st));
+    HIPCHK(trace_exclusive_scan(d_cnt.p, d_off.p, tiles + 1, st));  // (synchronises st)
+    HIPCHK(hipEventRecord(ev.e[1], st));
+    int64_t total = 0, gathered = 0;
+    unsigned long long gath[kImpactShards * kImpactShardStride] = {};
+    HIPCHK(hipMemcpy(&total, d_off.p + tiles, sizeof(int64_t), hipMemcpyDeviceToHost));
+    const int64_t nw = std::min(total, cap);
+    if (nw > 0) {
+        HIPCHK(d_out.ensure((size_t)nw));
+        HIPCHK(d_gath.ensure(sizeof gath / 8));
+        HIPCHK(hipMemsetAsync(d_gath.p, 0, sizeof gath, st));
+        HIPCHK(hipEventRecord(ev.e[2], st));
+        HIPCHK(launch_shift_fill(in, d_words.p, d_cnt.p, d_off.p, d_out.p, cap, d_gath.p, st));
+        HIPCHK(hipEventRecord(ev.e[3], st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+    ss->kernel_ms = ms;
+    if (nw > 0) {
+        HIPCHK(hipEventElapsedTime(&ms, ev.e[2], ev.e[3]));
+        ss->kernel_ms += ms;
+        HIPCHK(hipMemcpy(gath, d_gath.p, sizeof gath, hipMemcpyDeviceToHost));
+        for (unsigned long long x : gath) gathered += (int64_t)x;
+        HIPCHK(hipMemcpy(out, d_out.p, sizeof(ShiftRec) * (size_t)nw, hipMemcpyDeviceToHost));
+    }
+    unsigned long long tot[SH_COUNT], pval[SP_COUNT];
+    int64_t pidx[SP_COUNT];
+    HIPCHK(hipMemcpy(tot, d_tot.p, sizeof tot, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(pval, d_pval.p, sizeof pval, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(pidx, d_pidx.p, sizeof pidx, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 3; k++) {
+        tt->changed[k] = (int64_t)tot[SH_CHANGED + k];
+        tt->gained[k] = (int64_t)tot[SH_GAINED + k];
+        tt->lost[k] = (int64_t)tot[SH_LOST + k];
+        tt->newlyUsed[k] = (int64_t)tot[SH_NEW + k];
+        tt->abandoned[k] = (int64_t)tot[SH_ABANDONED + k];
+        tt->gainedWeight[k] = tot[SH_GAINED_W + k];
+        tt->lostWeight[k] = tot[SH_LOST_W + k];
+    }
+    tt->displaced = tot[SH_DISPLACED];
+    tt->appeared = tot[SH_APPEARED];
+    tt->worstGain = pval[SP_GAIN];
+    tt->worstGainIndex = pidx[SP_GAIN];
+    tt->worstLoss = pval[SP_LOSS];
+    tt->worstLossIndex = pidx[SP_LOSS];
+    tt->peakBefore = pval[SP_PEAK_BEFORE];
+    tt->peakBeforeIndex = pidx[SP_PEAK_BEFORE];
+    tt->peakAfter = pval[SP_PEAK_AFTER];
+    tt->peakAfterIndex = pidx[SP_PEAK_AFTER];
+    ss->words_skipped = (X + 63) / 64 - gathered;
+    ss->bytes_model = 8 * (2 * in.a.E + V) + 8 * (2 * in.b.E + V) + 8 * nwords +
+                      (8 + 16 * SP_COUNT) * tiles + (16 + 32) * nw;
+    return total;
+}
+
+// the shift under both build locks; a's statistics are the caller's to store
+int64_t shift_locked(Topology* a, Topology* b, const uint32_t* srcIP, const uint32_t* dstIP,
+                     const uint64_t* weight, int64_t n, ShdLoadChange* out, int64_t cap,
+                     ShdShiftTotals* tt, ShdShiftStats* ss) {
+    const int64_t R = root_edges(a), V = a->g.V;
+    *tt = ShdShiftTotals{};
+    tt->flows = n;
+    tt->worstGainIndex = tt->worstLossIndex = tt->peakBeforeIndex = tt->peakAfterIndex = -1;
+    ss->entries = 2 * R + V;
+    ss->words_skipped = (ss->entries + 63) / 64;
+    ShiftLoad la, lb;
+    la.top = a;
+    lb.top = b;
+    if (!root_gaps(a, R, la.gaps) || (a != b && !root_gaps(b, R, lb.gaps))) return -7;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<int32_t> sv, dv;
+    const int64_t nvalid = resolve_requests(a, srcIP, dstIP, n, sv, dv);
+    ss->resolve_ms = ms_since(t0);
+    tt->unattached = n - nvalid;
+    ShiftLoad& rb = a == b ? la : lb;
+    const bool host = a->isComplete && b->isComplete;
+    if (nvalid == 0) {  // nothing is routed on either side: every load is 0, no device is used
+        la.ls.requests = n;
+        la.ls.unattached = n;
+        ss->loadA = ss->loadB = la.ls;
+        return 0;
+    }
+    if (!host) {  // this thread's HIP device = both sides'
+        int r = dev_init(a);
+        if (!r && a != b) r = dev_init(b);
+        if (r) return r;
+        if (a->devId != b->devId) return -6;
+    }
+    int r = shift_accumulate(la, sv, dv, weight, n, nvalid);
+    if (!r && !host && la.onHost) r = shift_upload(la);
+    ss->load_a_ms = la.ms;
+    ss->loadA = ss->loadB = la.ls;
+    if (!r && a != b) {
+        r = shift_accumulate(lb, sv, dv, weight, n, nvalid);
+        if (!r && !host && lb.onHost) r = shift_upload(lb);
+        ss->load_b_ms = lb.ms;
+        ss->loadB = lb.ls;
+    }
+    if (r) return r;
+    tt->routedA = la.ls.routed;
+    tt->brokenA = la.ls.broken;
+    tt->hopWeightA = la.ls.hop_weight;
+    tt->routedB = rb.ls.routed;
+    tt->brokenB = rb.ls.broken;
+    tt->hopWeightB = rb.ls.hop_weight;
+    if (host) return shift_on_host(la, rb, R, V, out, cap, tt);
+    r = dev_init(a);  // (b's accumulation bound b's stream's device: the same one)
+    if (r) return r;
+    return shift_on_device(a, la, rb, R, V, out, cap, tt, ss);
+}
+
+int64_t load_shift(Topology* a, Topology* b, const uint32_t* srcIP, const uint32_t* dstIP,
+                   const uint64_t* weight, int64_t n, ShdLoadChange* out, int64_t cap,
+                   ShdShiftTotals* totals) {
+    if (!a || !b || n < 0 || n > 0x7FFFFFFE || cap < 0 || (cap > 0 && !out)) return -1;
+    if (n > 0 && (!srcIP || !dstIP)) return -1;
+    const auto t0 = std::chrono::steady_clock::now();
+    Topology* lo = std::less<Topology*>()(b, a) ? b : a;
+    Topology* hi = lo == a ? b : a;
+    std::unique_lock<std::mutex> l1(lo->buildMu);
+    std::unique_lock<std::mutex> l2;
+    if (hi != lo) l2 = std::unique_lock<std::mutex>(hi->buildMu);
+    if (a->g.V != b->g.V || root_edges(a) != root_edges(b)) return -7;
+    compute_geometry(a);
+    if (a != b) compute_geometry(b);
+    if (a->attached != b->attached) return -4;
+    ShdShiftTotals scratch;
+    ShdShiftStats ss{};
+    const int64_t total = shift_locked(a, b, srcIP, dstIP, weight, n, out, cap,
+                                       totals ? totals : &scratch, &ss);
+    ss.changed = total < 0 ? 0 : total;
+    ss.total_ms = ms_since(t0);
+    a->shiftStats = ss;
+    return total;
+}
+
 }  // namespace
 
 }  // namespace shdtopo
@@ -473,6 +814,7 @@ Topology* shdtopo_derive_without(Topology* top, const int32_t* failEdge, int64_t
     if (!top->edgeOrigin.empty())
         for (int32_t& e : origin) e = top->edgeOrigin[(size_t)e];
     c->edgeOrigin = std::move(origin);
+    c->rootE = root_edges(top);
     if (anyV) c->failedVertex = std::move(dropV);
     c->preChecked = true;
     const double copyMs = lap();
@@ -571,6 +913,20 @@ int64_t shdtopo_flow_impact_device(Topology* a, Topology* b, const int32_t* d_sr
 int shdtopo_flow_impact_stats(Topology* a, ShdImpactStats* out) {
     const int r = copy_stats(a, &_Topology::impactStats, out);
     if (!r) out->tile_flows = impact_tile_flows();
+    return r;
+}
+
+// ---- load shift (include/shd_topology_abi.h) ----
+
+int64_t shdtopo_load_shift(Topology* a, Topology* b, const uint32_t* srcIP, const uint32_t* dstIP,
+                           const uint64_t* weight, int64_t n, ShdLoadChange* out, int64_t cap,
+                           ShdShiftTotals* totals) {
+    return load_shift(a, b, srcIP, dstIP, weight, n, out, cap, totals);
+}
+
+int shdtopo_load_shift_stats(Topology* a, ShdShiftStats* out) {
+    const int r = copy_stats(a, &_Topology::shiftStats, out);
+    if (!r) out->tile_entries = shift_tile_entries();
     return r;
 }
 

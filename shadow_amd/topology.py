@@ -94,6 +94,11 @@ FLOW_CHANGE_DTYPE = np.dtype([("flow", np.int64), ("lat0", np.float64), ("lat1",
                               ("hops1", np.uint16), ("kind", np.uint32)])
 
 
+# one record of Topology.load_shift (ShdLoadChange)
+LOAD_CHANGE_DTYPE = np.dtype([("kind", np.int32), ("id", np.int32), ("idA", np.int32),
+                              ("idB", np.int32), ("before", np.uint64), ("after", np.uint64)])
+
+
 def crossings_by_watch(result):
     """Invert a Topology.link_crossings result into {watch index: flow indices} -- every watch of
     the call, the flows ascending, a flow once per record (host side: the records are already in
@@ -739,6 +744,63 @@ class Topology:
         if self._lib.shdtopo_flow_impact_stats(self._h, ctypes.byref(s)) != 0:
             raise RuntimeError("shdtopo_flow_impact_stats failed")
         return {k: getattr(s, k) for k, _ in L.ShdImpactStats._fields_}
+
+    def load_shift(self, other, src_ips, dst_ips, weight=None, cap=None):
+        """shdtopo_load_shift: where the load of the flows (src_ips[i] -> dst_ips[i], weight[i];
+        None: 1 each) differs between this topology (``before``) and ``other`` (``after``), both
+        accumulated as link_load does and compared on the device in the root topology's numbering
+        (``edge_origin()``).  With R root edges and V vertices, entry x < R is the forward half of
+        root edge x, R <= x < 2 R the reverse half of root edge x - R, x >= 2 R vertex x - 2 R.
+        Returns a dict: ``total``, the number of changed entries; ``records``
+        (LOAD_CHANGE_DTYPE: kind 0 / 1 / 2, id, idA / idB = the edge's id in this topology / in
+        ``other``, -1 where it lacks the edge), the first min(total, cap) in ascending x (cap=None
+        sizes the buffer with a cap = 0 call first); and the fields of ShdShiftTotals (the
+        per-kind ones as arrays of 3).  Every sum is a u64 that wraps."""
+        s = np.ascontiguousarray(src_ips, dtype=np.uint32)
+        d = np.ascontiguousarray(dst_ips, dtype=np.uint32)
+        if s.shape != d.shape or s.ndim != 1:
+            raise ValueError("src_ips and dst_ips must be 1-D and of one length")
+        w = None
+        if weight is not None:
+            w = np.ascontiguousarray(weight, dtype=np.uint64)
+            if w.shape != s.shape:
+                raise ValueError("weight must have one entry per flow")
+        n = len(s)
+
+        def call(out, c, totals):
+            return int(self._lib.shdtopo_load_shift(
+                self._h, other._h, _p(s) if n else None, _p(d) if n else None,
+                _p(w) if w is not None else None, n, out, c, totals))
+        if cap is None:
+            cap = call(None, 0, None)
+            if cap < 0:
+                raise RuntimeError("shdtopo_load_shift failed: %d" % cap, cap)
+        cap = int(cap)
+        tt = L.ShdShiftTotals()
+        records = np.zeros(max(cap, 1), LOAD_CHANGE_DTYPE)
+        total = call(_p(records) if cap else None, cap, ctypes.byref(tt))
+        if total < 0:
+            raise RuntimeError("shdtopo_load_shift failed: %d" % total, total)
+        res = {"total": total, "records": records[:min(total, cap)]}
+        for k, t in L.ShdShiftTotals._fields_:
+            v = getattr(tt, k)
+            if isinstance(v, ctypes.Array):
+                v = np.array(list(v), np.uint64 if t._type_ is L.u64 else np.int64)
+            res[k] = v
+        return res
+
+    def load_shift_stats(self):
+        """The last load_shift's own counters, kept by its first topology
+        (shdtopo_load_shift_stats); ``loadA`` / ``loadB`` are dicts with the fields of
+        link_load_stats for each side's accumulation, ``tile_entries`` is the build's tile,
+        256 x U entries."""
+        s = L.ShdShiftStats()
+        if self._lib.shdtopo_load_shift_stats(self._h, ctypes.byref(s)) != 0:
+            raise RuntimeError("shdtopo_load_shift_stats failed")
+        out = {k: getattr(s, k) for k, _ in L.ShdShiftStats._fields_}
+        for side in ("loadA", "loadB"):
+            out[side] = {k: getattr(out[side], k) for k, _ in L.ShdLoadStats._fields_}
+        return out
 
     def write_graphml(self, path):
         if self._lib.shdtopo_write_graphml(self._h, path.encode()) != 0:
