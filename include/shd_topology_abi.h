@@ -145,7 +145,10 @@ Topology* shdtopo_new_from_buffer(const char* graphml, size_t len);
  * rejected), "h0_seed" (1, the default: the batch kernel's landmark bound d_j(h0) of source j
  * starts at the graph preparation's d(s_j, h0), scaled up by max(1e-9, 4 V 2^-53), instead of
  * +inf, so the landmark filter, the target skip and the kappa cut prune from the first expansion;
- * 0: the bound is learnt from the kernel's tentative value of h0 alone; both give the same table).
+ * 0: the bound is learnt from the kernel's tentative value of h0 alone; both give the same table),
+ * "matrix_mb" (the bytes a traffic matrix's cells may take, a double in MB; 0, the default: half
+ * of the device memory free when the matrix grows, no cap for host cells; a negative value is
+ * rejected).
  * Returns 0 or -1 for an unknown key / bad value. */
 int shdtopo_set_option(Topology* top, const char* key, double value);
 
@@ -1199,6 +1202,136 @@ int shdtopo_synth_packets(Topology* top, uint64_t seed, int64_t n_hosts, int64_t
                           uint64_t t0, uint64_t jump, int32_t* srcCol, int32_t* dstCol,
                           uint32_t* payload, uint32_t* stateIn, uint64_t* now,
                           uint32_t* srcIP, uint32_t* dstIP);
+
+/* ---- traffic matrix: packet windows summed into per-pair flows ----
+ * Every analysis call of the family -- shdtopo_link_load, shdtopo_link_crossings,
+ * shdtopo_link_timeline, shdtopo_flow_impact, shdtopo_load_shift -- takes a set of flows (source
+ * host, destination host, weight).  A traffic matrix makes that set from a run: a persistent
+ * object of its topology, fed like a link monitor, that sums packets and weight per (source
+ * vertex, destination vertex) and exports its non-zero cells in order.  It needs no table, no
+ * chains and no routes, only the column geometry.
+ *
+ * Layout.  The matrix owns an ascending list mv of M original vertex ids and M x M cells of 16 B,
+ * {u64 packets, u64 weight}, row-major, row = source, column = destination.  mv starts empty.
+ * Before counting anything every feed compares the current column geometry (the columns
+ * shdtopo_route_batch_device sees, those deferred by shdtopo_window_hold included) with mv; if an
+ * attached vertex is missing the matrix grows: mv' is the sorted union, new cells are allocated
+ * and every old cell moves to its new place (a re-layout).  A vertex that later loses its column
+ * keeps its row, its column and its totals for good.  If 16 M'^2 bytes exceed option "matrix_mb"
+ * (a double, MB; 0, the default: half of the device memory free at that growth, no cap for host
+ * cells) the growth and the feed return -5 -- tested before anything is allocated; nothing is
+ * counted and the matrix, with its old mv, is untouched.
+ *
+ * A complete topology's host feeds accumulate in host cells and initialise no device; its device
+ * feeds use device cells.  Every other topology stages its host arrays and runs the feed kernel.
+ * A read that finds only host cells is answered on the host; one that finds both first adds the
+ * host cells into the device cells and clears them.
+ *
+ * Every sum is a u64 that wraps.  No output depends on the order of the feeds, on how the packets
+ * are split into feeds, on tiling or on scheduling.
+ *
+ * Matrices are small integer ids of their topology, as monitors are: a stale id or another
+ * topology's id returns -1 from every call and dereferences nothing; shdtopo_topology_free
+ * releases what is left.
+ *
+ *   shdtopo_matrix_new       id >= 0; uses no device.
+ *   shdtopo_matrix_feed      host arrays; the IPs resolve as in shdtopo_monitor_feed (an end that
+ *                            is no column: unattached, skipped and counted).  Packets with
+ *                            delivered[i] == 0 are skipped and counted.  Each remaining packet
+ *                            adds 1 to packets and weight[i] (NULL: 1) to weight of its cell; a
+ *                            self pair goes to the diagonal.  Returns the packets this feed
+ *                            counted.  -1: a NULL end array with n > 0, n < 0 or n > 2^31 - 2.
+ *   shdtopo_matrix_feed_vertices  the same with original vertex ids (-1 = not attached).
+ *   shdtopo_matrix_feed_device    the arrays of shdtopo_route_batch_device, resident in device
+ *                            memory; enqueued on `stream` (NULL: the library's), not awaited;
+ *                            returns 0 or a negative error.  A column outside [0, A) is skipped
+ *                            and counted (bad_columns), nothing is read through it.  The matrix
+ *                            owns one event: each device feed records it on its stream, a feed on
+ *                            another stream than the previous one first waits on it.
+ *   shdtopo_matrix_vertices  mv (the first min(M, cap) entries; out may be NULL); returns M.
+ *   shdtopo_matrix_read      the reported cells -- those with packets != 0 || weight != 0 -- as
+ *                            ShdMatrixFlow records in ascending (srcVertex, dstVertex) order;
+ *                            returns their number.  out gets the first min(total, cap) of them,
+ *                            nothing at or beyond cap is touched; cap = 0 with out = NULL sizes
+ *                            the buffer.  Every other output is complete whatever cap is; any
+ *                            output pointer may be NULL.  sent* are the row sums, recv* the column
+ *                            sums over all cells (u64[M] each).
+ *   shdtopo_matrix_reset     zeroes the cells and the cumulative counters; keeps mv.
+ *   shdtopo_matrix_stats     counters and sizes, below.
+ *   shdtopo_vertex_ips       per vertex the attached IP (network order) that is lowest when read
+ *                            in host byte order, 0 when no host is on it; returns the vertices
+ *                            that got one, -1 for bad arguments or a vertex outside [0, V).  Host
+ *                            only.  It turns exported cells into flows the rest of the family
+ *                            accepts: routes depend on the vertex alone, so any host of the
+ *                            vertex stands for it.
+ * read, stats, reset, vertices and free synchronise the matrix's event and the library's stream
+ * first.  The n == 0 feed launches nothing.
+ *
+ * Every call takes the build lock; none materialises a lazy row, pushes a minimum, builds or
+ * invalidates a table; each leaves ShdStats and every other statistic of the family as it was.
+ * A multi-device topology uses its first device. */
+typedef struct {
+    int32_t  srcVertex, dstVertex;  /* original vertex ids */
+    int32_t  srcIndex, dstIndex;    /* their places in mv */
+    uint64_t packets, weight;
+} ShdMatrixFlow;
+
+typedef struct {
+    int64_t  size;                  /* M */
+    int64_t  cells;                 /* reported cells */
+    uint64_t packets, weight;       /* over all cells */
+    int64_t  selfCells;             /* reported cells on the diagonal */
+    uint64_t selfPackets, selfWeight;
+    int64_t  activeSources;         /* rows with a reported cell */
+    int64_t  activeDestinations;    /* columns with a reported cell */
+    uint64_t peakWeight;            /* the largest weight of a reported cell (0: none) */
+    int64_t  peakCell;              /* the lowest i * M + j reaching it; -1: no reported cell */
+} ShdMatrixTotals;
+
+typedef struct {
+    double  feed_kernel_ms;         /* event time of the last feed's kernel (0: none, host cells) */
+    double  read_ms;                /* wall time of the last read */
+    double  read_kernel_ms;         /* of it: event time of the count, scan and fill passes */
+    double  relayout_ms;            /* wall time of the last growth */
+    /* cumulative since matrix_new / matrix_reset */
+    int64_t fed;                    /* packets counted */
+    int64_t skipped_undelivered;    /* delivered[i] == 0 */
+    int64_t unattached;             /* host feeds: an end that is no column */
+    int64_t bad_columns;            /* device feeds: a column outside [0, A) */
+    /* the last feed alone */
+    int64_t last_fed, last_skipped_undelivered, last_unattached, last_bad_columns;
+    int64_t feeds;                  /* feed calls since matrix_new */
+    int64_t size;                   /* M */
+    int64_t bytes;                  /* 16 M^2 */
+    int64_t relayouts;              /* growths that moved cells (an empty matrix moves none) */
+    int64_t cells;                  /* reported cells of the last read */
+    int64_t bytes_model;            /* the last read's modelled traffic: 16 M^2 (count) + 16 M per
+                                       row the fill walked + 32 per record written; a feed's
+                                       model is 8 B of columns + the weight (4, 8 or 0) + 1 B of
+                                       delivered per packet and two atomics on one 16-B cell */
+} ShdMatrixStats;
+
+int shdtopo_matrix_new(Topology* top);
+int shdtopo_matrix_free(Topology* top, int id);
+int64_t shdtopo_matrix_feed(Topology* top, int id, const uint32_t* srcIP, const uint32_t* dstIP,
+                            const uint64_t* weight /* NULL: 1 each */,
+                            const uint8_t* delivered /* NULL: all */, int64_t n);
+int64_t shdtopo_matrix_feed_vertices(Topology* top, int id, const int32_t* srcVertex,
+                                     const int32_t* dstVertex, const uint64_t* weight,
+                                     const uint8_t* delivered, int64_t n);
+int shdtopo_matrix_feed_device(Topology* top, int id, const int32_t* d_srcCol,
+                               const int32_t* d_dstCol,
+                               const uint32_t* d_payload /* weight; NULL: 1 each */,
+                               const uint8_t* d_delivered /* NULL: all */, int64_t n,
+                               void* stream);
+int64_t shdtopo_matrix_vertices(Topology* top, int id, int32_t* out, int64_t cap);
+int64_t shdtopo_matrix_read(Topology* top, int id, ShdMatrixFlow* out, int64_t cap,
+                            uint64_t* sentPackets, uint64_t* sentWeight, uint64_t* recvPackets,
+                            uint64_t* recvWeight /* u64[M] each; may be NULL */,
+                            ShdMatrixTotals* totals /* may be NULL */);
+int shdtopo_matrix_reset(Topology* top, int id);
+int shdtopo_matrix_stats(Topology* top, int id, ShdMatrixStats* out);
+int64_t shdtopo_vertex_ips(Topology* top, const int32_t* vertex, int64_t n, uint32_t* ip);
 
 #ifdef __cplusplus
 }

@@ -77,6 +77,15 @@ int topowindow_flush(TopoWindow* w, uint64_t jumpNs, int multiThreaded, TopoWind
 int topowindow_set_monitor(TopoWindow* w, int monitor /* -1: none */,
                            int bytes /* 1: weight = payloadLength, 0: 1 per packet */);
 
+/* Feed every flushed window to a traffic matrix of the topology (shdtopo_matrix_new,
+ * shd_topology_abi.h; -1: none), independently of and next to topowindow_set_monitor: after a
+ * successful route and before the window's deferred columns are released, topowindow_flush
+ * passes the window's packets with `delivered` from the batch's outputs to
+ * shdtopo_matrix_feed_vertices -- weight payloadLength (bytes = 1) or 1 per packet (bytes = 0).
+ * A feed error is logged and does not fail the flush.  Returns 0, -1 for a NULL window. */
+int topowindow_set_matrix(TopoWindow* w, int matrix /* -1: none */,
+                          int bytes /* 1: weight = payloadLength, 0: 1 per packet */);
+
 /* multi-threaded window (the reference's runahead, shd-master.c:98-124): (u64) minimum latency
  * in whole ms -- here the eager global minimum (topology_getMinimumLatency) -- 10 ms if unknown,
  * raised to runaheadNs (--runahead).  Inter-host arrivals are clamped to now + this. */

@@ -115,6 +115,27 @@ class ShdMonitorStats(ctypes.Structure):
                 ("batch_fallback", i64), ("broken_pairs", i64)]
 
 
+class ShdMatrixFlow(ctypes.Structure):
+    _fields_ = [("srcVertex", i32), ("dstVertex", i32), ("srcIndex", i32), ("dstIndex", i32),
+                ("packets", u64), ("weight", u64)]
+
+
+class ShdMatrixTotals(ctypes.Structure):
+    _fields_ = [("size", i64), ("cells", i64), ("packets", u64), ("weight", u64),
+                ("selfCells", i64), ("selfPackets", u64), ("selfWeight", u64),
+                ("activeSources", i64), ("activeDestinations", i64), ("peakWeight", u64),
+                ("peakCell", i64)]
+
+
+class ShdMatrixStats(ctypes.Structure):
+    _fields_ = [("feed_kernel_ms", dbl), ("read_ms", dbl), ("read_kernel_ms", dbl),
+                ("relayout_ms", dbl), ("fed", i64), ("skipped_undelivered", i64),
+                ("unattached", i64), ("bad_columns", i64), ("last_fed", i64),
+                ("last_skipped_undelivered", i64), ("last_unattached", i64),
+                ("last_bad_columns", i64), ("feeds", i64), ("size", i64), ("bytes", i64),
+                ("relayouts", i64), ("cells", i64), ("bytes_model", i64)]
+
+
 class ShdTableChange(ctypes.Structure):
     _fields_ = [("srcCol", i32), ("dstCol", i32), ("lat0", dbl), ("lat1", dbl), ("rel0", dbl),
                 ("rel1", dbl), ("hops0", ctypes.c_uint16), ("hops1", ctypes.c_uint16),
@@ -237,6 +258,16 @@ SIGNATURES = {
     "shdtopo_monitor_reset": (ctypes.c_int, [P, ctypes.c_int]),
     "shdtopo_monitor_stats": (ctypes.c_int, [P, ctypes.c_int, P]),
     "shdtopo_monitor_export_index": (i64, [P, ctypes.c_int, P, P, P, i64]),
+    "shdtopo_matrix_new": (ctypes.c_int, [P]),
+    "shdtopo_matrix_free": (ctypes.c_int, [P, ctypes.c_int]),
+    "shdtopo_matrix_feed": (i64, [P, ctypes.c_int, P, P, P, P, i64]),
+    "shdtopo_matrix_feed_vertices": (i64, [P, ctypes.c_int, P, P, P, P, i64]),
+    "shdtopo_matrix_feed_device": (ctypes.c_int, [P, ctypes.c_int, P, P, P, P, i64, P]),
+    "shdtopo_matrix_vertices": (i64, [P, ctypes.c_int, P, i64]),
+    "shdtopo_matrix_read": (i64, [P, ctypes.c_int, P, i64, P, P, P, P, P]),
+    "shdtopo_matrix_reset": (ctypes.c_int, [P, ctypes.c_int]),
+    "shdtopo_matrix_stats": (ctypes.c_int, [P, ctypes.c_int, P]),
+    "shdtopo_vertex_ips": (i64, [P, P, i64, P]),
     "shdtopo_derive_without": (P, [P, P, i64, P, i64, P]),
     "shdtopo_edge_origin": (i64, [P, P, i64]),
     "shdtopo_table_diff": (i64, [P, P, P, i64, P, P, P, P]),
@@ -269,6 +300,7 @@ SIGNATURES.update({
     "topowindow_jump_ns": (u64, [P, u64]),
     "topowindow_serial_window_ns": (u64, [P]),
     "topowindow_set_monitor": (ctypes.c_int, [P, ctypes.c_int, ctypes.c_int]),
+    "topowindow_set_matrix": (ctypes.c_int, [P, ctypes.c_int, ctypes.c_int]),
 })
 
 SHIM_SIGNATURES = {

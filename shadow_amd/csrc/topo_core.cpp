@@ -1725,6 +1725,7 @@ void topology_free(Topology* top) {
     for (Topology* p : top->peers) topology_free(p);
     top->peers.clear();
     monitors_release(top);
+    matrices_release(top);
     release_comms(top);
     if (top->devInit) {
         (void)hipStreamSynchronize(top->stream);
@@ -1814,6 +1815,10 @@ int shdtopo_set_option(Topology* top, const char* key, double value) {
     else if (k == "monitor_index_mb") {
         if (!(value >= 0)) return -1;
         top->monitorIndexMb = value;
+    }
+    else if (k == "matrix_mb") {
+        if (!(value >= 0)) return -1;
+        top->matrixMb = value;
     }
     else if (k == "tie_dense") top->tieDenseOpt = value < 0 ? -1 : (value != 0 ? 1 : 0);
     else if (k == "source_order") top->sourceOrder = (int)value;

@@ -627,6 +627,67 @@ hipError_t launch_monitor_feed_u64(int64_t n, const int32_t* src, const int32_t*
                                    const uint8_t* delivered, const MonIndex& ix, const TimeBins& tb,
                                    unsigned long long* cnt, hipStream_t stream);
 
+// ---- traffic matrix (topo_matrix.hip): packet windows summed into per-pair cells ----
+// one cell of the M x M matrix (row = source, column = destination): the two sums of a packet's
+// adds share a line, the export loads 16 B per cell
+struct __attribute__((aligned(16))) MatCell {
+    unsigned long long packets, weight;
+};
+// one reported cell: the device image of ShdMatrixFlow (include/shd_topology_abi.h), 32 B
+struct __attribute__((aligned(16))) MatFlowRec {
+    int32_t srcVertex, dstVertex, srcIndex, dstIndex;
+    unsigned long long packets, weight;
+};
+// counters of a matrix (u64 words): [0, MX_COUNT) cumulative, [MX_COUNT, 2 MX_COUNT) the last
+// feed's (zeroed by the caller before it)
+enum { MX_FED = 0, MX_SKIPPED, MX_BAD, MX_COUNT };
+// the u64 totals of one read's count pass (zeroed by the caller)
+enum {
+    MT_CELLS = 0, MT_PACKETS, MT_WEIGHT, MT_SELF_CELLS, MT_SELF_PACKETS, MT_SELF_WEIGHT,
+    MT_ACTIVE_SRC, MT_COUNT
+};
+// Feed: packet k (skipped when delivered[k] == 0; counted MX_BAD, nothing read through it, when a
+// column is outside [0, A) or colMap holds no index in [0, M) for it) adds 1 and its weight
+// (payload[k], NULL: 1) to cell (colMap[src[k]], colMap[dst[k]]).  Enqueued, not awaited.
+hipError_t launch_matrix_feed(int64_t n, const int32_t* src, const int32_t* dst,
+                              const uint32_t* payload, const uint8_t* delivered,
+                              const int32_t* colMap, int32_t A, MatCell* cells, int32_t M,
+                              unsigned long long* cnt, hipStream_t stream);
+// the same with u64 weights (the host feeds)
+hipError_t launch_matrix_feed_u64(int64_t n, const int32_t* src, const int32_t* dst,
+                                  const unsigned long long* weight, const uint8_t* delivered,
+                                  const int32_t* colMap, int32_t A, MatCell* cells, int32_t M,
+                                  unsigned long long* cnt, hipStream_t stream);
+// Re-layout: old cell (i, j) of the M0 x M0 matrix goes to (map[i], map[j]) of the M1 x M1 one
+// (map: i32[M0], strictly ascending, every entry in [0, M1)); the new cells are zeroed first.
+hipError_t launch_matrix_relayout(const MatCell* old, int32_t M0, const int32_t* map,
+                                  MatCell* cells, int32_t M1, hipStream_t stream);
+// cells[k] += add[k] for k < n (the uploaded host cells of a read)
+hipError_t launch_matrix_add(MatCell* cells, const MatCell* add, int64_t n, hipStream_t stream);
+// Count: one workgroup per row i: rowCells[i] = its reported cells (packets != 0 || weight != 0),
+// sentP / sentW [i] = its sums over all cells, rowPeakW / rowPeakCell [i] = the largest weight of
+// a reported cell and the lowest i M + j reaching it (0 / -1: none); recvP / recvW [j] += the
+// reported cells of column j, colActive[j] = 1 for a column with one (u64[M] / u32[M], zeroed by
+// the caller); tot: the MT_ totals.
+struct MatCount {
+    int64_t* rowCells = nullptr;
+    unsigned long long* sentP = nullptr;
+    unsigned long long* sentW = nullptr;
+    unsigned long long* recvP = nullptr;
+    unsigned long long* recvW = nullptr;
+    uint32_t* colActive = nullptr;
+    unsigned long long* rowPeakW = nullptr;
+    int64_t* rowPeakCell = nullptr;
+    unsigned long long* tot = nullptr;
+};
+hipError_t launch_matrix_count(const MatCell* cells, int32_t M, const MatCount& o,
+                               hipStream_t stream);
+// Fill: row i writes its reported cells' records, columns ascending, at out[rowOff[i]] .. (rowOff:
+// the exclusive scan of rowCells); records at or past cap are not written.  mv: i32[M].
+hipError_t launch_matrix_fill(const MatCell* cells, int32_t M, const int32_t* mv,
+                              const int64_t* rowCells, const int64_t* rowOff, MatFlowRec* out,
+                              int64_t cap, hipStream_t stream);
+
 // ---- table diff (topo_diff.hip): the changed pairs of two A x A tables ----
 // one changed pair: the device image of ShdTableChange (include/shd_topology_abi.h); hops =
 // hops0 | hops1 << 16

@@ -1,5 +1,5 @@
 // topo_host.h -- what the host units of libshdtopo (topo_core.cpp, topo_build.cpp, topo_flows.cpp,
-// topo_monitor_host.cpp, topo_whatif.cpp) share: logging, DevBuf, DevEvents, struct _Topology, the
+// topo_monitor_host.cpp, topo_matrix_host.cpp, topo_whatif.cpp) share: logging, DevBuf, DevEvents, struct _Topology, the
 // core functions the table build, the flow analysis and the what-if family call and the flow
 // analysis' own shared parts.  Included by the .cpp units only.
 #pragma once
@@ -124,6 +124,8 @@ uint64_t next_topology_uid();
 // link monitors (shdtopo_monitor_*, topo_monitor_host.cpp): ids are unique in the process, so
 // another topology's id is never found in this one's list
 struct LinkMonitor;
+// traffic matrices (shdtopo_matrix_*, topo_matrix_host.cpp): ids likewise
+struct TrafficMatrix;
 
 }  // namespace shdtopo
 using namespace shdtopo;
@@ -429,6 +431,10 @@ struct _Topology {
     // "monitor_index_mb" (0 = half of the free device memory at prepare)
     std::vector<std::pair<int, LinkMonitor*>> monitors;
     double monitorIndexMb = 0.0;
+    // traffic matrices (shdtopo_matrix_*, topo_matrix.hip): {id, matrix}; option "matrix_mb" (0 =
+    // half of the free device memory at a growth; host cells: no cap)
+    std::vector<std::pair<int, TrafficMatrix*>> matrices;
+    double matrixMb = 0.0;
 
     // multi-GPU build inside the library (one Shadow process): device d builds
     // rows [d*R, (d+1)*R) with its own stream / workspace (a peer Topology on that device),
@@ -578,6 +584,9 @@ int copy_stats(Topology* top, S _Topology::*field, S* out) {
 
 // ---- topo_monitor_host.cpp ----
 void monitors_release(Topology* top);
+
+// ---- topo_matrix_host.cpp ----
+void matrices_release(Topology* top);
 
 // ---- topo_flows.cpp: the parts of the flow analysis the link monitor shares ----
 

@@ -33,6 +33,8 @@ struct _TopoWindow {
     std::vector<TopoPacketOut> out;
     int monitor = -1;         // topowindow_set_monitor: the link monitor fed at every flush
     bool monitorBytes = true;  // its weight: payloadLength, else 1 per packet
+    int matrix = -1;          // topowindow_set_matrix: the traffic matrix fed at every flush
+    bool matrixBytes = true;   // its weight: payloadLength, else 1 per packet
 };
 
 extern "C" {
@@ -92,6 +94,14 @@ int topowindow_set_monitor(TopoWindow* w, int monitor, int bytes) {
     return 0;
 }
 
+int topowindow_set_matrix(TopoWindow* w, int matrix, int bytes) {
+    if (!w) return -1;
+    std::lock_guard<std::mutex> lk(w->mu);
+    w->matrix = matrix < 0 ? -1 : matrix;
+    w->matrixBytes = bytes != 0;
+    return 0;
+}
+
 int topowindow_flush(TopoWindow* w, uint64_t jumpNs, int multiThreaded, TopoWindowDeliver deliver,
                      void* ctx) {
     if (!w) return -1;
@@ -129,25 +139,39 @@ int topowindow_flush(TopoWindow* w, uint64_t jumpNs, int multiThreaded, TopoWind
         w->in.swap(in);
         return r;
     }
-    // the link monitor sees the window before its deferred columns go: the packets the batch
-    // delivered, at their emission times.  A feed error costs the monitor the window, not the run.
-    int monitor;
-    bool bytes;
+    // the link monitor and the traffic matrix see the window before its deferred columns go: the
+    // packets the batch delivered, at their emission times.  A feed error costs the monitor or the
+    // matrix the window, not the run.
+    int monitor, matrix;
+    bool bytes, mbytes;
     {
         std::lock_guard<std::mutex> lk(w->mu);
         monitor = w->monitor;
         bytes = w->monitorBytes;
+        matrix = w->matrix;
+        mbytes = w->matrixBytes;
+    }
+    std::vector<uint64_t> wt;
+    std::vector<uint8_t> dl;
+    if (monitor >= 0 || matrix >= 0) {
+        dl.resize(n);
+        if ((monitor >= 0 && bytes) || (matrix >= 0 && mbytes)) wt.assign(pay.begin(), pay.end());
+        for (size_t i = 0; i < n; i++) dl[i] = w->out[i].delivered ? 1 : 0;
     }
     if (monitor >= 0) {
-        std::vector<uint64_t> wt;
-        std::vector<uint8_t> dl(n);
-        if (bytes) wt.assign(pay.begin(), pay.end());
-        for (size_t i = 0; i < n; i++) dl[i] = w->out[i].delivered ? 1 : 0;
         const int64_t fr = shdtopo_monitor_feed_vertices(w->top, monitor, sv.data(), dv.data(),
                                                          bytes ? wt.data() : nullptr, now.data(),
                                                          dl.data(), (int64_t)n);
         if (fr < 0)
             WARNING("link monitor %d: feeding a window of %lld packets failed: %lld", monitor,
+                    (long long)n, (long long)fr);
+    }
+    if (matrix >= 0) {
+        const int64_t fr = shdtopo_matrix_feed_vertices(w->top, matrix, sv.data(), dv.data(),
+                                                        mbytes ? wt.data() : nullptr, dl.data(),
+                                                        (int64_t)n);
+        if (fr < 0)
+            WARNING("traffic matrix %d: feeding a window of %lld packets failed: %lld", matrix,
                     (long long)n, (long long)fr);
     }
     // the window's packets are routed: vertices detached during it may leave the table now

@@ -597,6 +597,23 @@ class Topology:
         route_batch_device) without walking a route."""
         return LinkMonitor(self, edges, vertices, t0, bin_ns, nbins)
 
+    # ---- traffic matrix ----
+    def traffic_matrix(self):
+        """shdtopo_matrix_new: a TrafficMatrix of this topology -- packets and weight summed per
+        (source vertex, destination vertex) over every fed window, exported as flows."""
+        return TrafficMatrix(self)
+
+    def vertex_ips(self, vertices):
+        """shdtopo_vertex_ips: per vertex the attached IP (network order) that is lowest when
+        read in host byte order, 0 for a vertex without hosts."""
+        v = np.ascontiguousarray(vertices, dtype=np.int32).reshape(-1)
+        ip = np.zeros(len(v), np.uint32)
+        r = int(self._lib.shdtopo_vertex_ips(self._h, _p(v) if len(v) else None, len(v),
+                                             _p(ip) if len(v) else None))
+        if r < 0:
+            raise ValueError("shdtopo_vertex_ips failed: %d" % r)
+        return ip
+
     # ---- link failure what-if ----
     def without(self, edges=(), vertices=()):
         """shdtopo_derive_without: a new, independent Topology without the given edges (edge ids)
@@ -990,6 +1007,122 @@ class LinkMonitor:
     def free(self):
         if self.id >= 0:
             self._lib.shdtopo_monitor_free(self._top._h, self.id)
+            self.id = -1
+
+
+MATRIX_FLOW = np.dtype([("srcVertex", np.int32), ("dstVertex", np.int32), ("srcIndex", np.int32),
+                        ("dstIndex", np.int32), ("packets", np.uint64), ("weight", np.uint64)])
+
+
+class TrafficMatrix:
+    """A traffic matrix (include/shd_topology_abi.h, "traffic matrix"): after any sequence of
+    feeds, ``read()`` is the per-(source vertex, destination vertex) sum of all fed packets and
+    ``flows()`` the same as flows the analysis calls (link_load, flow_impact, ...) accept."""
+
+    def __init__(self, topology):
+        self._top = topology
+        self._lib = topology._lib
+        self.id = int(self._lib.shdtopo_matrix_new(topology._h))
+        if self.id < 0:
+            raise RuntimeError("shdtopo_matrix_new failed: %d" % self.id)
+
+    def _check(self, r, what):
+        if r < 0:
+            raise RuntimeError("shdtopo_matrix_%s failed: %d" % (what, r), r)
+        return r
+
+    def _feed(self, fn, what, a, b, dtype, weight, delivered):
+        s = np.ascontiguousarray(a, dtype=dtype)
+        d = np.ascontiguousarray(b, dtype=dtype)
+        if s.shape != d.shape or s.ndim != 1:
+            raise ValueError("the two ends must be 1-D and of one length")
+        opt = []
+        for x, t, name in ((weight, np.uint64, "weight"), (delivered, np.uint8, "delivered")):
+            if x is not None:
+                x = np.ascontiguousarray(x, dtype=t)
+                if x.shape != s.shape:
+                    raise ValueError("%s must have one entry per packet" % name)
+            opt.append(x)
+        w, dl = opt
+        return self._check(int(fn(self._top._h, self.id, _p(s), _p(d),
+                                  _p(w) if w is not None else None,
+                                  _p(dl) if dl is not None else None, len(s))), what)
+
+    def feed(self, src_ips, dst_ips, weight=None, delivered=None):
+        """Feed packets given by host IPs (numpy / sequences); the packets this feed counted."""
+        return self._feed(self._lib.shdtopo_matrix_feed, "feed", src_ips, dst_ips, np.uint32,
+                          weight, delivered)
+
+    def feed_vertices(self, src_v, dst_v, weight=None, delivered=None):
+        """The same by original vertex ids (-1: not attached)."""
+        return self._feed(self._lib.shdtopo_matrix_feed_vertices, "feed_vertices", src_v, dst_v,
+                          np.int32, weight, delivered)
+
+    def feed_device(self, src_col, dst_col, payload=None, delivered=None, stream=0):
+        """Feed the device arrays of route_batch_device (torch tensors used as plain HBM buffers:
+        int32 columns, uint32-sized payload, uint8 delivered).  Enqueued on ``stream``, not
+        awaited."""
+        ptr = lambda x: x.data_ptr() if x is not None else None
+        self._check(int(self._lib.shdtopo_matrix_feed_device(
+            self._top._h, self.id, src_col.data_ptr(), dst_col.data_ptr(), ptr(payload),
+            ptr(delivered), int(src_col.numel()), stream or None)), "feed_device")
+
+    def vertices(self):
+        """The matrix's vertex list mv (ascending original vertex ids)."""
+        m = self._check(int(self._lib.shdtopo_matrix_vertices(self._top._h, self.id, None, 0)),
+                        "vertices")
+        out = np.zeros(m, np.int32)
+        if m:
+            self._check(int(self._lib.shdtopo_matrix_vertices(self._top._h, self.id, _p(out), m)),
+                        "vertices")
+        return out
+
+    def read(self, cap=None):
+        """``(records, sums, totals)``: the reported cells (a MATRIX_FLOW structured array in
+        ascending (srcVertex, dstVertex) order, the first ``cap`` of them when given), a dict of
+        the four u64[M] sum arrays (sentPackets, sentWeight, recvPackets, recvWeight) and a dict
+        of ShdMatrixTotals (``cells`` counts every reported cell whatever ``cap`` is)."""
+        h, lib = self._top._h, self._lib
+        if cap is None:
+            cap = self._check(int(lib.shdtopo_matrix_read(h, self.id, None, 0, None, None, None,
+                                                          None, None)), "read")
+        cap = int(cap)
+        m = len(self.vertices())
+        rec = np.zeros(max(cap, 1), MATRIX_FLOW)
+        names = ("sentPackets", "sentWeight", "recvPackets", "recvWeight")
+        sums = {k: np.zeros(m, np.uint64) for k in names}
+        tot = L.ShdMatrixTotals()
+        n = self._check(int(lib.shdtopo_matrix_read(
+            h, self.id, _p(rec) if cap else None, cap,
+            *[_p(sums[k]) if m else None for k in names], ctypes.byref(tot))), "read")
+        return (rec[:min(n, cap)], sums,
+                {k: getattr(tot, k) for k, _ in L.ShdMatrixTotals._fields_})
+
+    def flows(self, cap=None):
+        """``(src_ips, dst_ips, weight, packets)`` of the reported cells, each vertex standing
+        in with its lowest attached IP (Topology.vertex_ips): what link_load, link_crossings,
+        link_timeline, flow_impact and load_shift accept.  Records whose source or destination
+        vertex has no host any more are dropped; ``self.dropped`` is their number."""
+        rec, _, _ = self.read(cap)
+        ips = self._top.vertex_ips(self.vertices())
+        s, d = ips[rec["srcIndex"]], ips[rec["dstIndex"]]
+        keep = (s != 0) & (d != 0)
+        self.dropped = int(len(rec) - keep.sum())
+        return (s[keep], d[keep], np.ascontiguousarray(rec["weight"][keep]),
+                np.ascontiguousarray(rec["packets"][keep]))
+
+    def reset(self):
+        self._check(int(self._lib.shdtopo_matrix_reset(self._top._h, self.id)), "reset")
+
+    def stats(self):
+        s = L.ShdMatrixStats()
+        self._check(int(self._lib.shdtopo_matrix_stats(self._top._h, self.id, ctypes.byref(s))),
+                    "stats")
+        return {k: getattr(s, k) for k, _ in L.ShdMatrixStats._fields_}
+
+    def free(self):
+        if self.id >= 0:
+            self._lib.shdtopo_matrix_free(self._top._h, self.id)
             self.id = -1
 
 
