@@ -1333,6 +1333,82 @@ int shdtopo_matrix_reset(Topology* top, int id);
 int shdtopo_matrix_stats(Topology* top, int id, ShdMatrixStats* out);
 int64_t shdtopo_vertex_ips(Topology* top, const int32_t* vertex, int64_t n, uint32_t* ip);
 
+/* ---- route schedule: packets routed by the topology live at their emit time ----
+ * The what-if family compares a topology with a derived one offline; a schedule puts the two into
+ * one run: a link fails at t = 40 s and comes back at t = 70 s.  A schedule is k topologies
+ * tops[0..k) with start times fromNs[0..k): 1 <= k <= SHD_SCHEDULE_MAX, fromNs[0] == 0, fromNs
+ * strictly ascending.  The same topology may appear in several epochs ([parent, child, parent]).
+ * Every member must have the same attached vertices as tops[0] (a derived topology carries its
+ * parent's hosts), so a column means the same host vertex in every table.
+ *
+ * Semantics.  Packet i belongs to epoch e(i), the largest e with fromNs[e] <= now[i], and its
+ * outputs (time, rngState, delivered) are bit for bit what shdtopo_route_batch_device on
+ * tops[e(i)] alone returns for it: the {lat, rel} gather at [srcCol][dstCol], the rand_r steps and
+ * the chance <= rel || payload == 0 rule, the (uint64_t)ceil(lat * 1000000.0) delay, the clamp; a
+ * column outside [0, A) gives delivered 0, time 0 and the state unchanged.  The route is decided
+ * at emission, as worker_schedulePacket decides it: a packet emitted before a failure and
+ * arriving after it is delivered.  The schedule always reads the forward row [src][dst] of each
+ * table, like the device route: it emulates no lazy orientation, materialises no lazy row, pushes
+ * no minimum and leaves ShdStats and every family statistic as they were (its counters and timing
+ * events are its own).  A table it had to build counts as a build like any other.
+ *
+ * Outputs.  d_epoch / epoch (may be NULL) receives e(i), one byte per packet.  epochCount (host
+ * u64[k][3], may be NULL): {packets of epoch e, of them delivered, of them not routed}, exact
+ * counts reduced on the device, independent of tiling; a packet that is not routed still has an
+ * epoch, taken from its now.
+ *
+ * Variants.  The device variant takes the arrays of shdtopo_route_batch_device and runs its
+ * kernel on `stream` (NULL: tops[0]'s own) behind whatever is enqueued there; it returns when the
+ * kernel is done, so the tables stay locked while they are read, and returns 0.  The host
+ * variants resolve vertices (and IPs) through tops[0], with shdtopo_route_batch_vertices' rule for
+ * a vertex that is no column: the packet is not routed -- delivered 0, time 0, rngState the state
+ * after its one draw -- and they return the number of such packets.  n = 0 with valid arguments
+ * returns 0 and builds nothing.
+ *
+ * Errors: -1 bad arguments (NULL tops or a NULL member, k outside [1, 16], fromNs[0] != 0, fromNs
+ * not strictly ascending, n < 0, a NULL array with n > 0); -4 the members' attached vertex lists
+ * are not all identical; -6 the tables are not all on one device; -5 the attached sets kept
+ * changing under the call.  Argument errors and -4 are returned before any device is used.
+ * Missing tables are built as by shdtopo_build, then the build locks of the distinct members are
+ * taken in address order.  A multi-device member is read on its first device.
+ *
+ * Device work (topo_schedule.hip): packet_route_kernel's tile with the k table pointers and start
+ * times passed by value; 53 B per packet as the one-table route (24 B in, a 16-B gather, 13 B
+ * out), plus 1 B with d_epoch.  shdtopo_route_schedule_stats reads the statistics of the last
+ * call whose tops[0] was `first`. */
+#define SHD_SCHEDULE_MAX 16
+typedef struct {
+    double  total_ms;       /* wall time of the call (table builds it had to wait for included) */
+    double  kernel_ms;      /* event time of the kernel (events of the call's own) */
+    int64_t packets;        /* n */
+    int64_t epochs;         /* k */
+    int64_t not_routed;     /* packets with a column outside [0, A) / a vertex that is no column */
+    int64_t epoch_packets[SHD_SCHEDULE_MAX];
+    int64_t epoch_delivered[SHD_SCHEDULE_MAX];
+    int64_t bytes_model;    /* 53 B per packet, 54 with the epoch output */
+} ShdScheduleStats;
+
+int64_t shdtopo_route_schedule_device(Topology* const* tops, const uint64_t* fromNs, int k,
+                                      const int32_t* d_srcCol, const int32_t* d_dstCol,
+                                      const uint32_t* d_payload, const uint32_t* d_stateIn,
+                                      const uint64_t* d_now, int64_t n, uint64_t jumpNs, int clamp,
+                                      uint64_t* d_time, uint32_t* d_stateOut, uint8_t* d_delivered,
+                                      uint8_t* d_epoch /* may be NULL */,
+                                      uint64_t* epochCount /* host u64[k][3], may be NULL */,
+                                      void* stream);
+int64_t shdtopo_route_schedule_vertices(Topology* const* tops, const uint64_t* fromNs, int k,
+                                        const int32_t* srcVertex, const int32_t* dstVertex,
+                                        const uint32_t* payloadLength, const uint32_t* rngState,
+                                        const uint64_t* now, int64_t n, uint64_t jumpNs,
+                                        int clampInterHost, TopoPacketOut* out,
+                                        uint8_t* epoch /* host, may be NULL */,
+                                        uint64_t* epochCount);
+int64_t shdtopo_route_schedule(Topology* const* tops, const uint64_t* fromNs, int k,
+                               const TopoPacketIn* in, TopoPacketOut* out, int64_t n,
+                               uint64_t jumpNs, int clampInterHost, uint8_t* epoch,
+                               uint64_t* epochCount);
+int shdtopo_route_schedule_stats(Topology* first, ShdScheduleStats* out);
+
 #ifdef __cplusplus
 }
 #endif

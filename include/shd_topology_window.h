@@ -86,6 +86,22 @@ int topowindow_set_monitor(TopoWindow* w, int monitor /* -1: none */,
 int topowindow_set_matrix(TopoWindow* w, int matrix /* -1: none */,
                           int bytes /* 1: weight = payloadLength, 0: 1 per packet */);
 
+/* Route every flushed window through a route schedule (shd_topology_abi.h, "route schedule"): k
+ * topologies with their start times, each packet routed by the one live at its emission time.
+ * tops[0] must be the window's topology (else -1); k = 0 clears the schedule; otherwise the
+ * arguments are validated as by shdtopo_route_schedule_vertices (-1: a NULL array or member, k
+ * outside [1, 16], fromNs[0] != 0, fromNs not strictly ascending).  While a schedule is set the
+ * adapter holds shdtopo_window_hold(+1) on every other distinct member (dropped, with a release,
+ * when the schedule is cleared or replaced and at topowindow_free), so a host the caller detaches
+ * on every member during a window keeps its column on all of them; topowindow_flush routes with
+ * shdtopo_route_schedule_vertices and calls shdtopo_window_release on every member after a
+ * successful route; a negative result puts the window back as without a schedule.  The caller
+ * mirrors every attach and detach on all members.  The monitor and matrix feeds stay as they
+ * are: a link monitor's hit index describes tops[0]'s routes, so under a schedule it is right
+ * for the packets of the epochs that hold tops[0] alone; the traffic matrix walks no route and
+ * stays exact.  Returns 0. */
+int topowindow_set_schedule(TopoWindow* w, Topology* const* tops, const uint64_t* fromNs, int k);
+
 /* multi-threaded window (the reference's runahead, shd-master.c:98-124): (u64) minimum latency
  * in whole ms -- here the eager global minimum (topology_getMinimumLatency) -- 10 ms if unknown,
  * raised to runaheadNs (--runahead).  Inter-host arrivals are clamped to now + this. */

@@ -188,6 +188,15 @@ class ShdShiftStats(ctypes.Structure):
                 ("loadB", ShdLoadStats)]
 
 
+SCHEDULE_MAX = 16  # SHD_SCHEDULE_MAX
+
+
+class ShdScheduleStats(ctypes.Structure):
+    _fields_ = [("total_ms", dbl), ("kernel_ms", dbl), ("packets", i64), ("epochs", i64),
+                ("not_routed", i64), ("epoch_packets", i64 * SCHEDULE_MAX),
+                ("epoch_delivered", i64 * SCHEDULE_MAX), ("bytes_model", i64)]
+
+
 class ShdSynthParams(ctypes.Structure):
     _fields_ = [("seed", u64), ("n_routers", i64), ("n_poi", i64), ("n_edges", i64),
                 ("integer_latency", ctypes.c_int), ("alpha", dbl), ("directed", ctypes.c_int)]
@@ -277,6 +286,12 @@ SIGNATURES = {
     "shdtopo_flow_impact_stats": (ctypes.c_int, [P, P]),
     "shdtopo_load_shift": (i64, [P, P, P, P, P, i64, P, i64, P]),
     "shdtopo_load_shift_stats": (ctypes.c_int, [P, P]),
+    "shdtopo_route_schedule_device": (i64, [P, P, ctypes.c_int, P, P, P, P, P, i64, u64,
+                                            ctypes.c_int, P, P, P, P, P, P]),
+    "shdtopo_route_schedule_vertices": (i64, [P, P, ctypes.c_int, P, P, P, P, P, i64, u64,
+                                              ctypes.c_int, P, P, P]),
+    "shdtopo_route_schedule": (i64, [P, P, ctypes.c_int, P, P, i64, u64, ctypes.c_int, P, P]),
+    "shdtopo_route_schedule_stats": (ctypes.c_int, [P, P]),
     "shdtopo_test_segsort": (ctypes.c_int, [P, i64, P, i64, ctypes.c_int, P, P]),
     "shdtopo_test_batch_layout": (ctypes.c_int, [P, i64, dbl, ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_int, P, P, P]),
@@ -301,6 +316,7 @@ SIGNATURES.update({
     "topowindow_serial_window_ns": (u64, [P]),
     "topowindow_set_monitor": (ctypes.c_int, [P, ctypes.c_int, ctypes.c_int]),
     "topowindow_set_matrix": (ctypes.c_int, [P, ctypes.c_int, ctypes.c_int]),
+    "topowindow_set_schedule": (ctypes.c_int, [P, P, P, ctypes.c_int]),
 })
 
 SHIM_SIGNATURES = {

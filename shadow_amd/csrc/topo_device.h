@@ -837,6 +837,26 @@ hipError_t launch_packet_route(int64_t n, const int32_t* src, const int32_t* dst
                                uint64_t jump, int clamp, uint64_t* t_out, uint32_t* state_out,
                                uint8_t* delivered, unsigned long long* d_bad, hipStream_t stream);
 
+// ---- route schedule (topo_schedule.hip): each packet routed by the table live at its emit time ----
+// The k tables (A x A each, on the current device) and their start times, passed to the kernel by
+// value: wave-uniform, so they arrive in SGPRs.  from[0] = 0, from strictly ascending; entries at
+// and past k are not read.
+constexpr int kScheduleMax = 16;
+struct ScheduleTables {
+    const double2* lr[kScheduleMax] = {};
+    unsigned long long from[kScheduleMax] = {};
+    int32_t k = 0;
+};
+// launch_packet_route with the table of epoch e(i) = the largest e with from[e] <= now[i] for
+// packet i; epoch (nullable) receives e(i), one byte per packet; cnt (u64 [k][3], zeroed by the
+// caller): {packets, delivered, columns outside [0, A)} of every epoch.  Enqueued, not awaited.
+hipError_t launch_route_schedule(const ScheduleTables& t, int64_t n, const int32_t* src,
+                                 const int32_t* dst, const uint32_t* payload,
+                                 const uint32_t* state_in, const uint64_t* now, int64_t A,
+                                 uint64_t jump, int clamp, uint64_t* t_out, uint32_t* state_out,
+                                 uint8_t* delivered, uint8_t* epoch, unsigned long long* cnt,
+                                 hipStream_t stream);
+
 hipError_t launch_row_min(int64_t rows, int64_t A, const double2* lr, double* out_rowmin,
                           hipStream_t stream);
 

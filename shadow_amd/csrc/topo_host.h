@@ -152,6 +152,11 @@ struct _Topology {
     ShdDiffStats diffStats{};  // table diff (shdtopo_table_diff, topo_diff.hip): first argument's
     ShdImpactStats impactStats{};  // flow impact (shdtopo_flow_impact, topo_impact.hip): likewise
     ShdShiftStats shiftStats{};    // load shift (shdtopo_load_shift, topo_shift.hip): likewise
+    // route schedule (shdtopo_route_schedule*, topo_schedule.hip): tops[0]'s -- the last call's
+    // statistics, the call's epoch counters (u64 [16][3]) and the host variants' epoch bytes
+    ShdScheduleStats scheduleStats{};
+    DevBuf<unsigned long long> d_schedCnt;
+    DevBuf<uint8_t> b_ep;
 
     // options ("abort_on_error" and "lazy" are read by getters on worker threads without a lock)
     std::atomic<bool> abortOnError{true};

@@ -5,7 +5,9 @@
 // kernels in topo_shift.hip).  The diff and the impact compare the resident tables of two
 // topologies: one driver, with_current_pair, takes their locks and brings the tables up to date
 // for both.  The shift needs no table: it takes both locks itself, runs the link load's
-// accumulation (topo_flows.cpp) on each side and compares the two results where they are.
+// accumulation (topo_flows.cpp) on each side and compares the two results where they are.  The
+// route schedule (shdtopo_route_schedule*; kernel in topo_schedule.hip) reads the resident tables
+// of up to 16 topologies in one packet route: with_current_set is the pair driver over a set.
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
@@ -54,6 +56,32 @@ int64_t with_current_pair(Topology* a, Topology* b, bool sameNeedsTable, const c
         if (r) return r;
     }
     CRITICAL("the attached sets keep changing while the %s are compared", what);
+    return -5;
+}
+
+// The same driver over a set of topologies (the route schedule): mem holds distinct topologies in
+// ascending address order, which is the order their build locks are taken in.  locked() runs once
+// every member's attached set equals mem[0]'s (else -4) and, when needTables, every table stands;
+// stale tables are built outside the locks and the attempt repeated, -5 after four.
+template <class F>
+int64_t with_current_set(const std::vector<Topology*>& mem, bool needTables, const char* what,
+                         F&& locked) {
+    for (int attempt = 0; attempt < 4; attempt++) {
+        {
+            std::vector<std::unique_lock<std::mutex>> locks;
+            locks.reserve(mem.size());
+            for (Topology* m : mem) locks.emplace_back(m->buildMu);
+            for (Topology* m : mem) compute_geometry(m);
+            bool current = true;
+            for (Topology* m : mem) {
+                if (m->attached != mem[0]->attached) return -4;
+                current = current && table_current(m);
+            }
+            if (!needTables || current) return locked();
+        }
+        for (Topology* m : mem) CHK(ensure_table(m));
+    }
+    CRITICAL("the attached sets keep changing while the %s are read", what);
     return -5;
 }
 
@@ -731,6 +759,179 @@ int64_t load_shift(Topology* a, Topology* b, const uint32_t* srcIP, const uint32
     return total;
 }
 
+// ---- route schedule (shdtopo_route_schedule*; kernel in topo_schedule.hip) ----
+
+static_assert(SHD_SCHEDULE_MAX == kScheduleMax, "the ABI's limit is the kernel argument's");
+
+// one call: the schedule, the window (device variant: device arrays; host variant: vertices, -1 =
+// the address is not attached) and its outputs
+struct ScheduleCall {
+    Topology* const* tops = nullptr;
+    const uint64_t* fromNs = nullptr;
+    int k = 0;
+    bool onDevice = false;
+    const int32_t* src = nullptr;  // columns on the device / vertices on the host
+    const int32_t* dst = nullptr;
+    const uint32_t* payload = nullptr;
+    const uint32_t* stateIn = nullptr;
+    const uint64_t* now = nullptr;
+    int64_t n = 0;
+    uint64_t jumpNs = 0;
+    int clamp = 0;
+    uint64_t* d_time = nullptr;  // device variant
+    uint32_t* d_stateOut = nullptr;
+    uint8_t* d_delivered = nullptr;
+    TopoPacketOut* out = nullptr;  // host variant
+    uint8_t* epoch = nullptr;      // device / host array, may be NULL
+    uint64_t* epochCount = nullptr;
+    hipStream_t stream = nullptr;
+};
+
+bool schedule_ok(Topology* const* tops, const uint64_t* fromNs, int k) {
+    if (!tops || !fromNs || k < 1 || k > SHD_SCHEDULE_MAX || fromNs[0] != 0) return false;
+    for (int e = 0; e < k; e++)
+        if (!tops[e] || (e > 0 && fromNs[e] <= fromNs[e - 1])) return false;
+    return true;
+}
+
+bool args_ok(const ScheduleCall& c) {
+    if (!schedule_ok(c.tops, c.fromNs, c.k) || c.n < 0) return false;
+    if (c.n == 0) return true;
+    if (!c.src || !c.dst || !c.payload || !c.stateIn || !c.now) return false;
+    return c.onDevice ? c.d_time && c.d_stateOut && c.d_delivered : c.out != nullptr;
+}
+
+// the distinct members of a schedule in ascending address order
+std::vector<Topology*> schedule_members(Topology* const* tops, int k) {
+    std::vector<Topology*> mem(tops, tops + k);
+    std::sort(mem.begin(), mem.end(), std::less<Topology*>());
+    mem.erase(std::unique(mem.begin(), mem.end()), mem.end());
+    return mem;
+}
+
+// the schedule over current tables with equal attached sets; the caller holds every member's
+// build lock.  Returns the packets not routed (the device variant: 0).
+int64_t schedule_locked(const ScheduleCall& c, const std::vector<Topology*>& mem,
+                        ShdScheduleStats* ss) {
+    Topology* t0 = c.tops[0];
+    const int64_t A = t0->A;
+    const size_t n = (size_t)c.n;
+    const int k = c.k;
+    if (c.epochCount) std::fill(c.epochCount, c.epochCount + 3 * k, (uint64_t)0);
+    if (n == 0) return 0;
+    for (Topology* m : mem)
+        if (m->devId != t0->devId) return -6;
+    CHK(dev_init(t0));  // this thread's HIP device = the tables'
+    hipStream_t st = c.onDevice && c.stream ? c.stream : t0->stream;
+    // (each member's table was written on its own stream)
+    for (Topology* m : mem)
+        if (m->stream != st) HIPCHK(hipStreamSynchronize(m->stream));
+    ScheduleTables T;
+    T.k = k;
+    for (int e = 0; e < k; e++) {
+        T.lr[e] = tab_lr(c.tops[e]);
+        T.from[e] = c.fromNs[e];
+    }
+    const int32_t *d_src = c.src, *d_dst = c.dst;
+    const uint32_t *d_pay = c.payload, *d_sin = c.stateIn;
+    const uint64_t* d_now = c.now;
+    uint64_t* d_time = c.d_time;
+    uint32_t* d_sout = c.d_stateOut;
+    uint8_t *d_dl = c.d_delivered, *d_ep = c.epoch;
+    std::vector<int32_t> sc, dc;
+    int64_t bad = 0;
+    if (!c.onDevice) {
+        // the vertices' columns through tops[0], by route_vertices' rule; the staging is tops[0]'s
+        sc.resize(n);
+        dc.resize(n);
+        for (size_t i = 0; i < n; i++) {
+            sc[i] = c.src[i] >= 0 && c.src[i] < t0->g.V ? t0->colOf[(size_t)c.src[i]] : -1;
+            dc[i] = c.dst[i] >= 0 && c.dst[i] < t0->g.V ? t0->colOf[(size_t)c.dst[i]] : -1;
+            if (sc[i] < 0 || dc[i] < 0 || sc[i] >= A || dc[i] >= A) {
+                sc[i] = dc[i] = -1;  // not routed (the kernel leaves it undelivered)
+                bad++;
+            }
+        }
+        HIPCHK(t0->b_src.ensure(n)); HIPCHK(t0->b_dst.ensure(n)); HIPCHK(t0->b_pay.ensure(n));
+        HIPCHK(t0->b_sin.ensure(n)); HIPCHK(t0->b_sout.ensure(n)); HIPCHK(t0->b_now.ensure(n));
+        HIPCHK(t0->b_time.ensure(n)); HIPCHK(t0->b_dl.ensure(n));
+        if (c.epoch) HIPCHK(t0->b_ep.ensure(n));
+        HIPCHK(hipMemcpyAsync(t0->b_src.p, sc.data(), 4 * n, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(t0->b_dst.p, dc.data(), 4 * n, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(t0->b_pay.p, c.payload, 4 * n, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(t0->b_sin.p, c.stateIn, 4 * n, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(t0->b_now.p, c.now, 8 * n, hipMemcpyHostToDevice, st));
+        d_src = t0->b_src.p;
+        d_dst = t0->b_dst.p;
+        d_pay = t0->b_pay.p;
+        d_sin = t0->b_sin.p;
+        d_now = t0->b_now.p;
+        d_time = t0->b_time.p;
+        d_sout = t0->b_sout.p;
+        d_dl = t0->b_dl.p;
+        d_ep = c.epoch ? t0->b_ep.p : nullptr;
+    }
+    // counters and events of the call's own: ST_ROUTE_BAD, ev2 / ev3 and routePending are ShdStats'
+    HIPCHK(t0->d_schedCnt.ensure(3 * kScheduleMax));
+    DevEvents<2> ev;
+    CHK(ev.create());
+    HIPCHK(hipMemsetAsync(t0->d_schedCnt.p, 0, 8 * 3 * (size_t)k, st));
+    HIPCHK(hipEventRecord(ev.e[0], st));
+    HIPCHK(launch_route_schedule(T, c.n, d_src, d_dst, d_pay, d_sin, d_now, A, c.jumpNs, c.clamp,
+                                 d_time, d_sout, d_dl, d_ep, t0->d_schedCnt.p, st));
+    HIPCHK(hipEventRecord(ev.e[1], st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+    ss->kernel_ms = ms;
+    unsigned long long cnt[3 * kScheduleMax] = {};
+    HIPCHK(hipMemcpy(cnt, t0->d_schedCnt.p, 8 * 3 * (size_t)k, hipMemcpyDeviceToHost));
+    for (int e = 0; e < k; e++) {
+        ss->epoch_packets[e] = (int64_t)cnt[3 * e];
+        ss->epoch_delivered[e] = (int64_t)cnt[3 * e + 1];
+        ss->not_routed += (int64_t)cnt[3 * e + 2];
+    }
+    if (c.epochCount) std::copy(cnt, cnt + 3 * k, c.epochCount);
+    ss->bytes_model = c.n * (53 + (c.epoch ? 1 : 0));
+    if (c.onDevice) return 0;
+    std::vector<uint64_t> tim(n);
+    std::vector<uint32_t> sout(n);
+    std::vector<uint8_t> dl(n);
+    HIPCHK(hipMemcpy(tim.data(), d_time, 8 * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sout.data(), d_sout, 4 * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(dl.data(), d_dl, n, hipMemcpyDeviceToHost));
+    if (c.epoch) HIPCHK(hipMemcpy(c.epoch, d_ep, n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) {
+        c.out[i].time = tim[i];
+        c.out[i].rngState = sout[i];
+        if (sc[i] < 0) {  // not routed: the state after the sender's one draw
+            uint32_t s = c.stateIn[i];
+            (void)glibc_rand_r(&s);
+            c.out[i].rngState = s;
+        }
+        c.out[i].delivered = dl[i];
+        c.out[i]._pad[0] = c.out[i]._pad[1] = c.out[i]._pad[2] = 0;
+    }
+    if (bad) WARNING("%lld packets of a scheduled batch have an address that is not attached: "
+                     "not routed", (long long)bad);
+    return bad;
+}
+
+int64_t route_schedule(const ScheduleCall& c) {
+    if (!args_ok(c)) return -1;
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::vector<Topology*> mem = schedule_members(c.tops, c.k);
+    return with_current_set(mem, c.n > 0, "scheduled tables", [&] {
+        ShdScheduleStats ss{};
+        ss.packets = c.n;
+        ss.epochs = c.k;
+        const int64_t r = schedule_locked(c, mem, &ss);
+        ss.total_ms = ms_since(t0);
+        c.tops[0]->scheduleStats = ss;
+        return r;
+    });
+}
+
 }  // namespace
 
 }  // namespace shdtopo
@@ -928,6 +1129,92 @@ int shdtopo_load_shift_stats(Topology* a, ShdShiftStats* out) {
     const int r = copy_stats(a, &_Topology::shiftStats, out);
     if (!r) out->tile_entries = shift_tile_entries();
     return r;
+}
+
+// ---- route schedule (include/shd_topology_abi.h) ----
+
+int64_t shdtopo_route_schedule_device(Topology* const* tops, const uint64_t* fromNs, int k,
+                                      const int32_t* d_srcCol, const int32_t* d_dstCol,
+                                      const uint32_t* d_payload, const uint32_t* d_stateIn,
+                                      const uint64_t* d_now, int64_t n, uint64_t jumpNs, int clamp,
+                                      uint64_t* d_time, uint32_t* d_stateOut, uint8_t* d_delivered,
+                                      uint8_t* d_epoch, uint64_t* epochCount, void* stream) {
+    ScheduleCall c;
+    c.tops = tops;
+    c.fromNs = fromNs;
+    c.k = k;
+    c.onDevice = true;
+    c.src = d_srcCol;
+    c.dst = d_dstCol;
+    c.payload = d_payload;
+    c.stateIn = d_stateIn;
+    c.now = d_now;
+    c.n = n;
+    c.jumpNs = jumpNs;
+    c.clamp = clamp;
+    c.d_time = d_time;
+    c.d_stateOut = d_stateOut;
+    c.d_delivered = d_delivered;
+    c.epoch = d_epoch;
+    c.epochCount = epochCount;
+    c.stream = (hipStream_t)stream;
+    return route_schedule(c);
+}
+
+int64_t shdtopo_route_schedule_vertices(Topology* const* tops, const uint64_t* fromNs, int k,
+                                        const int32_t* srcVertex, const int32_t* dstVertex,
+                                        const uint32_t* payloadLength, const uint32_t* rngState,
+                                        const uint64_t* now, int64_t n, uint64_t jumpNs,
+                                        int clampInterHost, TopoPacketOut* out, uint8_t* epoch,
+                                        uint64_t* epochCount) {
+    ScheduleCall c;
+    c.tops = tops;
+    c.fromNs = fromNs;
+    c.k = k;
+    c.src = srcVertex;
+    c.dst = dstVertex;
+    c.payload = payloadLength;
+    c.stateIn = rngState;
+    c.now = now;
+    c.n = n;
+    c.jumpNs = jumpNs;
+    c.clamp = clampInterHost;
+    c.out = out;
+    c.epoch = epoch;
+    c.epochCount = epochCount;
+    return route_schedule(c);
+}
+
+int64_t shdtopo_route_schedule(Topology* const* tops, const uint64_t* fromNs, int k,
+                               const TopoPacketIn* in, TopoPacketOut* out, int64_t n,
+                               uint64_t jumpNs, int clampInterHost, uint8_t* epoch,
+                               uint64_t* epochCount) {
+    if (!schedule_ok(tops, fromNs, k) || n < 0 || (n > 0 && (!in || !out))) return -1;
+    const size_t m = (size_t)n;
+    std::vector<int32_t> sv(m), dv(m);
+    std::vector<uint32_t> pay(m), sin(m);
+    std::vector<uint64_t> now(m);
+    {
+        Topology* top = tops[0];
+        std::shared_lock<std::shared_mutex> lk(top->ipMu);
+        for (size_t i = 0; i < m; i++) {
+            auto a = top->virtualIP.find(in[i].srcIP);
+            auto b = top->virtualIP.find(in[i].dstIP);
+            sv[i] = a == top->virtualIP.end() ? -1 : a->second;
+            dv[i] = b == top->virtualIP.end() ? -1 : b->second;
+            pay[i] = in[i].payloadLength;
+            sin[i] = in[i].rngState;
+            now[i] = in[i].now;
+        }
+    }
+    // (n = 0: the empty vectors' data() may be NULL, which is what a window without packets gives)
+    return shdtopo_route_schedule_vertices(tops, fromNs, k, sv.data(), dv.data(), pay.data(),
+                                           sin.data(), now.data(), n, jumpNs, clampInterHost, out,
+                                           epoch, epochCount);
+}
+
+int shdtopo_route_schedule_stats(Topology* first, ShdScheduleStats* out) {
+    return copy_stats(first, &_Topology::scheduleStats, out);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // topo_window.cpp -- the engine-side window adapter (include/shd_topology_window.h, SURVEY.md
 // 8(f)#3): worker_schedulePacket (src/engine/shd-worker.c:332-370) recorded at emit and routed
 // as one GPU batch at the scheduler's window barrier (shd-slave.c:415-461).
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -35,7 +36,25 @@ struct _TopoWindow {
     bool monitorBytes = true;  // its weight: payloadLength, else 1 per packet
     int matrix = -1;          // topowindow_set_matrix: the traffic matrix fed at every flush
     bool matrixBytes = true;   // its weight: payloadLength, else 1 per packet
+    // topowindow_set_schedule: the members and start times every flush routes through (empty:
+    // none; sched[0] == top), and the distinct members besides top, each held by one
+    // shdtopo_window_hold(+1)
+    std::vector<Topology*> sched;
+    std::vector<uint64_t> schedFrom;
+    std::vector<Topology*> schedHeld;
 };
+
+namespace {
+// drop the holds of a schedule's other members; a column one kept for the window may go, unless
+// the member is held again by the schedule that follows (keep)
+void drop_schedule_holds(std::vector<Topology*>& held, const std::vector<Topology*>& keep = {}) {
+    for (Topology* m : held) {
+        shdtopo_window_hold(m, -1);
+        if (std::find(keep.begin(), keep.end(), m) == keep.end()) shdtopo_window_release(m);
+    }
+    held.clear();
+}
+}  // namespace
 
 extern "C" {
 
@@ -49,6 +68,7 @@ TopoWindow* topowindow_new(Topology* top) {
 
 void topowindow_free(TopoWindow* w) {
     if (!w) return;
+    drop_schedule_holds(w->schedHeld);
     shdtopo_window_hold(w->top, -1);
     shdtopo_window_release(w->top);
     delete w;
@@ -102,16 +122,47 @@ int topowindow_set_matrix(TopoWindow* w, int matrix, int bytes) {
     return 0;
 }
 
+int topowindow_set_schedule(TopoWindow* w, Topology* const* tops, const uint64_t* fromNs, int k) {
+    if (!w || k < 0 || k > SHD_SCHEDULE_MAX) return -1;
+    std::vector<Topology*> sched, held;
+    std::vector<uint64_t> from;
+    if (k > 0) {
+        if (!tops || !fromNs || tops[0] != w->top || fromNs[0] != 0) return -1;
+        for (int e = 0; e < k; e++)
+            if (!tops[e] || (e > 0 && fromNs[e] <= fromNs[e - 1])) return -1;
+        sched.assign(tops, tops + k);
+        from.assign(fromNs, fromNs + k);
+        for (Topology* m : sched)
+            if (m != w->top && std::find(held.begin(), held.end(), m) == held.end())
+                held.push_back(m);
+    }
+    // the new members are held before the old ones are let go: one that is in both keeps its
+    // deferred columns
+    for (Topology* m : held) shdtopo_window_hold(m, +1);
+    std::lock_guard<std::mutex> lk(w->mu);
+    drop_schedule_holds(w->schedHeld, held);
+    w->sched.swap(sched);
+    w->schedFrom.swap(from);
+    w->schedHeld.swap(held);
+    return 0;
+}
+
 int topowindow_flush(TopoWindow* w, uint64_t jumpNs, int multiThreaded, TopoWindowDeliver deliver,
                      void* ctx) {
     if (!w) return -1;
     std::vector<WinPacket> in;
+    std::vector<Topology*> sched, held;
+    std::vector<uint64_t> from;
     {
         std::lock_guard<std::mutex> lk(w->mu);
         in.swap(w->in);
+        sched = w->sched;
+        from = w->schedFrom;
+        held = w->schedHeld;
     }
     if (in.empty()) {
         shdtopo_window_release(w->top);
+        for (Topology* m : held) shdtopo_window_release(m);
         return 0;
     }
     const size_t n = in.size();
@@ -129,15 +180,23 @@ int topowindow_flush(TopoWindow* w, uint64_t jumpNs, int multiThreaded, TopoWind
     // a vertex detached during the window is still a column (shdtopo_window_hold): its packets
     // are routed as at emit; only a packet whose vertex left before an earlier flush comes back
     // undelivered
-    const int r = shdtopo_route_batch_vertices(w->top, sv.data(), dv.data(), pay.data(), st.data(),
-                                               now.data(), n, jumpNs, multiThreaded, w->out.data());
+    // (under a schedule each packet by the member live at its emission time; the members hold the
+    // same columns: the caller mirrors attach and detach on all of them)
+    const int64_t r =
+        sched.empty()
+            ? shdtopo_route_batch_vertices(w->top, sv.data(), dv.data(), pay.data(), st.data(),
+                                           now.data(), n, jumpNs, multiThreaded, w->out.data())
+            : shdtopo_route_schedule_vertices(sched.data(), from.data(), (int)sched.size(),
+                                              sv.data(), dv.data(), pay.data(), st.data(),
+                                              now.data(), (int64_t)n, jumpNs, multiThreaded,
+                                              w->out.data(), nullptr, nullptr);
     if (r < 0) {
         // nothing was routed: the window is put back in front of what was emitted meanwhile, so
         // a later flush routes every packet in emission order
         std::lock_guard<std::mutex> lk(w->mu);
         in.insert(in.end(), w->in.begin(), w->in.end());
         w->in.swap(in);
-        return r;
+        return (int)r;
     }
     // the link monitor and the traffic matrix see the window before its deferred columns go: the
     // packets the batch delivered, at their emission times.  A feed error costs the monitor or the
@@ -176,6 +235,7 @@ int topowindow_flush(TopoWindow* w, uint64_t jumpNs, int multiThreaded, TopoWind
     }
     // the window's packets are routed: vertices detached during it may leave the table now
     shdtopo_window_release(w->top);
+    for (Topology* m : held) shdtopo_window_release(m);
     if (deliver)
         for (size_t i = 0; i < n; i++)
             deliver(ctx, in[i].packet, w->out[i].delivered, w->out[i].time);

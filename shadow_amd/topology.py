@@ -1126,5 +1126,94 @@ class TrafficMatrix:
             self.id = -1
 
 
+PACKET_IN = np.dtype([("srcIP", np.uint32), ("dstIP", np.uint32), ("payloadLength", np.uint32),
+                      ("rngState", np.uint32), ("now", np.uint64)])
+PACKET_OUT = np.dtype([("time", np.uint64), ("rngState", np.uint32), ("delivered", np.uint8),
+                       ("_pad", np.uint8, 3)])
+
+
+class RouteSchedule:
+    """A route schedule (include/shd_topology_abi.h, "route schedule"): ``tops[e]`` routes the
+    packets emitted at or after ``from_ns[e]`` and before ``from_ns[e + 1]``; ``from_ns[0]`` is 0
+    and the start times ascend strictly.  The same topology may appear in several epochs, as in
+    ``[parent, child, parent]`` for a link that fails and comes back; every member needs the
+    attached vertices of ``tops[0]``.  The library validates the schedule at every call."""
+
+    def __init__(self, tops, from_ns):
+        self.tops = list(tops)
+        self.from_ns = np.ascontiguousarray(from_ns, dtype=np.uint64).reshape(-1)
+        if len(self.tops) != len(self.from_ns):
+            raise ValueError("one start time per topology")
+        self.k = len(self.tops)
+        self._lib = L.load()[0]
+        self._handles = (ctypes.c_void_p * max(self.k, 1))(
+            *[t._h if t is not None else None for t in self.tops])
+
+    def _check(self, r, what):
+        if r < 0:
+            raise RuntimeError("%s failed: %d" % (what, r), r)
+        return int(r)
+
+    def _host(self, what, call, n, want_epoch):
+        out = np.zeros(max(n, 1), PACKET_OUT)
+        epoch = np.zeros(max(n, 1), np.uint8) if want_epoch else None
+        count = np.zeros((max(self.k, 1), 3), np.uint64)
+        r = self._check(call(_p(out), _p(epoch) if want_epoch else None, _p(count)), what)
+        out = out[:n]
+        return (out["time"].copy(), out["delivered"].copy(), out["rngState"].copy(),
+                epoch[:n] if want_epoch else None, count[:self.k], r)
+
+    def route(self, src_ip, dst_ip, payload, rng_state, now, jump_ns, clamp=True, epoch=True):
+        """shdtopo_route_schedule: (time, delivered, state, epoch, epoch_count, not_routed) of the
+        packets given by their hosts' IPs, resolved through ``tops[0]``."""
+        n = len(src_ip)
+        ins = np.zeros(max(n, 1), PACKET_IN)
+        for name, x in (("srcIP", src_ip), ("dstIP", dst_ip), ("payloadLength", payload),
+                        ("rngState", rng_state), ("now", now)):
+            ins[name][:n] = x
+        return self._host("shdtopo_route_schedule", lambda out, ep, cnt:
+                          self._lib.shdtopo_route_schedule(
+                              self._handles, _p(self.from_ns), self.k, _p(ins), out, n,
+                              int(jump_ns), int(clamp), ep, cnt), n, epoch)
+
+    def route_vertices(self, src_v, dst_v, payload, rng_state, now, jump_ns, clamp=True,
+                       epoch=True):
+        """shdtopo_route_schedule_vertices: the same for packets given by their vertices."""
+        n = len(src_v)
+        c = lambda x, t: np.ascontiguousarray(x, dtype=t)
+        sv, dv = c(src_v, np.int32), c(dst_v, np.int32)
+        pay, st, nw = c(payload, np.uint32), c(rng_state, np.uint32), c(now, np.uint64)
+        return self._host("shdtopo_route_schedule_vertices", lambda out, ep, cnt:
+                          self._lib.shdtopo_route_schedule_vertices(
+                              self._handles, _p(self.from_ns), self.k, _p(sv), _p(dv), _p(pay),
+                              _p(st), _p(nw), n, int(jump_ns), int(clamp), out, ep, cnt), n, epoch)
+
+    def route_device(self, src_col, dst_col, payload, state_in, now, jump_ns, clamp, t_out,
+                     state_out, delivered, epoch=None, stream=0):
+        """shdtopo_route_schedule_device on the device arrays of Topology.route_batch_device
+        (torch tensors used as plain HBM buffers); ``epoch``: an optional uint8 tensor that
+        receives each packet's epoch.  The kernel runs on ``stream``; the call returns when it is
+        done.  Returns epoch_count, uint64 [k, 3]: packets, delivered, not routed per epoch."""
+        n = int(src_col.numel())
+        count = np.zeros((max(self.k, 1), 3), np.uint64)
+        ptr = lambda x: x.data_ptr() if n else None
+        self._check(self._lib.shdtopo_route_schedule_device(
+            self._handles, _p(self.from_ns), self.k, ptr(src_col), ptr(dst_col), ptr(payload),
+            ptr(state_in), ptr(now), n, int(jump_ns), int(clamp), ptr(t_out), ptr(state_out),
+            ptr(delivered), epoch.data_ptr() if epoch is not None and n else None, _p(count),
+            stream or None), "shdtopo_route_schedule_device")
+        return count[:self.k]
+
+    def stats(self):
+        """The last call's own counters, kept by ``tops[0]`` (shdtopo_route_schedule_stats)."""
+        s = L.ShdScheduleStats()
+        self._check(self._lib.shdtopo_route_schedule_stats(self.tops[0]._h, ctypes.byref(s)),
+                    "shdtopo_route_schedule_stats")
+        out = {k: getattr(s, k) for k, _ in L.ShdScheduleStats._fields_}
+        for f in ("epoch_packets", "epoch_delivered"):
+            out[f] = np.array(list(out[f]), np.int64)
+        return out
+
+
 def shim():
     return L.load()[1]
